@@ -20,7 +20,13 @@ the one-shot API instead (r1's definition; the reference recomputes everything p
 too (`value_one_shot`).  `--prepacked` takes the per-frame operands as given (prepared when the
 embeddings were produced).
 
-The ONE JSON line also carries, at N = 1, the other single-GPU BASELINE configs as `also` legs
+A plain run (the command above) sets up, warms up, times the K steps and prints the line: the headline with its `roofline` /
+`local_stage` figures, which come from the library's HIP events inside the timed steps.  `--dump-outputs DIR` writes what the
+last timed step returned (global map, merged global memory row, local map) as DIR/<name>.npy; the inputs are seeded, so
+two builds run with the same arguments compare output for output.  Everything below that needs runs of its own is behind
+`--full`.
+
+With `--full` the ONE JSON line also carries, at N = 1, the other single-GPU BASELINE configs as `also` legs
 (configs[2] = cfg3 and configs[4] = cfg5, bf16 arithmetic on 2-byte embeddings): ms per step, the
 dominant kernel's HIP-event time and roofline fraction, and their error against the fp32 oracle;
 `headline_exact_mode` (the headline workload through compute="bf16r": the fp32 bits at bf16 cost);
@@ -319,8 +325,9 @@ def run_leg(wl, K, Wm, args, lib, use_dist=False, one_shot=False, prepacked=Fals
     bank_rows, bank_lab, halo = build_bank(True)
     bank = prepare(bank_rows, bank_lab, bank)
     first_prev(halo)
-    for i in range(K):
+    for i in range(K - 1):
         step(i, bank, bank_rows, bank_lab, halo)
+    last = step(K - 1, bank, bank_rows, bank_lab, halo)  # (kept: what the caller of the last step receives)
     barrier()
     elapsed = time.perf_counter() - t0
     if bank is not None:
@@ -334,7 +341,8 @@ def run_leg(wl, K, Wm, args, lib, use_dist=False, one_shot=False, prepacked=Fals
     kern_ms = float(np.mean([ms[i] for i in range(nrec.value)])) if nrec.value else float("nan")
     local_ms = float(np.mean([lms[i] for i in range(nloc.value)])) if nloc.value else float("nan")
     return {"elapsed": elapsed, "kern_ms": kern_ms, "local_ms": local_ms, "prep_ms": prep_ms, "bank_rows": bank_rows,
-            "bank_lab": bank_lab, "collective": timing["collective"], "bank": bank}
+            "bank_lab": bank_lab, "collective": timing["collective"], "bank": bank,
+            "outputs": {"global_map": last[0], "global_memory": wl.gmap[(K - 1) % 104], "local_map": last[1]}}
 
 
 def roofline_blocks(wl, kern_ms, local_ms, overlap=False, prep_ms=None):
@@ -942,6 +950,20 @@ def compact_line(full):
     return out
 
 
+DUMP_LIMIT = 64 << 20  # bytes of `--dump-outputs` in all
+
+
+def dump_outputs(path, outputs):
+    """`--dump-outputs DIR`: the last timed step's results, whole, as float32 DIR/<name>.npy (under 5 MB at every config)"""
+    arrays = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py --dump-outputs: %d bytes, more than the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def emit(line):
     """rank 0: the full line to bench_full.json and to a prefixed stdout line, then the compact line LAST"""
     try:  # RCCL writes a version banner through C stdio: flush it first so the JSON line comes last
@@ -982,6 +1004,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check beyond the headline: at N = 1 the one-shot rate, the stored-volume local stage, the "
+                         "CPU baseline + parity and, for the default workload, `headline_exact_mode`, the `also` legs, "
+                         "`robustness` and `e2e` (the --no-* options drop single blocks).  A plain run times the headline only")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the last timed step returned (global_map, global_memory, local_map) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip every CPU-oracle leg (baseline + parity)")
     ap.add_argument("--no-also", action="store_true", help="skip the extra cfg3 / cfg5 bf16 legs of the N=1 line")
     ap.add_argument("--also-steps", type=int, default=40)
@@ -1007,7 +1035,7 @@ def main():
     ap.add_argument("--data", type=str, default="iid", choices=["iid", "video", "smooth", "flat"],
                     help="embedding distribution of the main leg (tools/synth_clip.py): iid = SURVEY 8d's relu(randn) with "
                          "uniform labels (the headline); video / smooth = spatially smooth, temporally redundant, "
-                         "label-coherent clips; flat = all rows of an object identical, the floor (N = 1 only).  The default line "
+                         "label-coherent clips; flat = all rows of an object identical, the floor (N = 1 only).  The --full line "
                          "brackets all of them in `robustness`.")
     ap.add_argument("--scale", type=float, default=0.1, help="embedding scale (SURVEY 8d: 0.1)")
     ap.add_argument("--no-robustness", action="store_true", help="skip the `robustness` legs of the N=1 line")
@@ -1028,6 +1056,10 @@ def main():
     backend = os.environ.get("MANET_BENCH_BACKEND", "nccl")
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.e2e and args.dump_outputs:
+        raise SystemExit("bench.py --dump-outputs: the matching-path line only (not --e2e)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under a launcher: become the launcher (no GPU call has happened in this process)
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -1093,6 +1125,8 @@ def main():
 
     line = None
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, r.pop("outputs"))
         bank_rows, bank_lab = r["bank_rows"], r["bank_lab"]
         M = int(bank_rows.shape[0])
         assert M == wl.T * wl.H * wl.W, "bank must hold T distinct frames"
@@ -1118,13 +1152,14 @@ def main():
             # what the collective of the timed region saw: a real N-rank run shows world == n_gpus and backend nccl
             "collective": r["collective"] if use_dist else None,
         }
-        if world == 1 and not use_dist and local is not None:
+        # everything past the headline takes runs of its own: --full only
+        if args.full and world == 1 and not use_dist and local is not None:
             local["stored_volume"] = stored_volume_block(wl, lib)
-        if world == 1 and not args.one_shot and not use_dist:
+        if args.full and world == 1 and not args.one_shot and not use_dist:
             # r1's definition next to the headline: the bank re-sorted / re-packed every frame, one-shot API
             r1s = run_leg(wl, min(K, 10), 2, args, lib, one_shot=True)
             line["value_one_shot"] = min(K, 10) / r1s["elapsed"]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the same frame once more on the GPU (fresh map, outside the timed region) for the parity figures
             p = wl.probe_frame()
             g_chk = ops.global_match(bank_rows, wl.frame_emb(p).permute(1, 2, 0), bank_lab, wl.n_ids, normalize=True,
@@ -1133,9 +1168,10 @@ def main():
                                     wl.prev_labs[0], wl.n_ids, wl.d)
             # (bf16 arithmetic on bf16-stored embeddings: the oracle's fp32 formula on the same stored values)
             line["cpu_baseline"], line["parity"] = cpu_baseline(wl, bank_rows, bank_lab, g_chk, l_chk)
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = None  # measured on rank 0 at N=1 only (see the N=1 line)
-        default_line = world == 1 and not use_dist and args.cfg == 2 and args.compute == "f32" and args.data == "iid"
+        default_line = (args.full and world == 1 and not use_dist and args.cfg == 2 and args.compute == "f32"
+                        and args.data == "iid")
         if default_line:
             del wl, r, bank_rows, bank_lab
             torch.cuda.empty_cache()

@@ -37,7 +37,7 @@ def test_two_rank_flow_on_one_gpu():
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "1",
-                        "--cfg", "3", "--compute", "bf16"], env=env, capture_output=True, text=True, timeout=600)
+                        "--cfg", "3", "--compute", "bf16", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     import json
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -259,13 +259,13 @@ def test_compact_line_of_the_r04_capture_fits_4k():
 
 @pytest.mark.gpu
 def test_default_command_last_line_is_compact_json():
-    """the driver's command (`python bench.py --steps K --warmup W`, everything else default): the LAST stdout line is valid JSON
-    under 4 KB with roofline.frac and cpu_baseline.value; the full blocks are on the `#bench_full ` line and in bench_full.json"""
+    """`python bench.py --steps K --warmup W --full`, everything else default: the LAST stdout line is valid JSON under 4 KB with
+    roofline.frac and cpu_baseline.value; the full blocks are on the `#bench_full ` line and in bench_full.json"""
     import json
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full"], env=env,
                        capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     lines = r.stdout.strip().splitlines()
@@ -285,3 +285,56 @@ def test_default_command_last_line_is_compact_json():
     full = json.loads(fulls[0][len("#bench_full "):])
     assert "legs" in full["robustness"] and full["value"] == pytest.approx(line["value"], rel=1e-4)
     assert json.load(open(os.path.join(ROOT, "bench_full.json")))["metric"] == line["metric"]
+
+
+def test_steps_must_be_positive():
+    """--steps sets the number of timed steps: zero is refused before anything starts"""
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in (r.stdout + r.stderr) and '"metric"' not in r.stdout
+
+
+@pytest.mark.gpu
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """the plain command times the headline only (no block of `--full`), and `--dump-outputs` writes what the last timed step
+    returned: the same bits from run to run, and the same as the stateless API's on the seeded inputs of that step"""
+    import json
+
+    import numpy as np
+    import torch
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    K = 3
+    dumps = []
+    for n in range(2):
+        d = str(tmp_path / ("run%d" % n))
+        line = _run_json([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "1",
+                          "--dump-outputs", d], env)
+        assert line["steps"] == K and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "f32"
+        assert line["value"] > 0 and line["ms_per_step"] == pytest.approx(1e3 / line["value"], rel=1e-3)
+        assert line["unit"] == "frames/s" and line["higher_is_better"] is True and 0.0 < line["roofline"]["frac"] < 1.0
+        for k in ("cpu_baseline", "parity", "value_one_shot", "headline_exact_mode", "also", "robustness", "e2e"):
+            assert k not in line, k
+        assert "phase2_us" not in line["local_stage"]
+        dumps.append({k: np.load(os.path.join(d, k + ".npy")) for k in ("global_map", "global_memory", "local_map")})
+    for k in dumps[0]:
+        assert dumps[0][k].dtype == np.float32
+        np.testing.assert_array_equal(dumps[0][k], dumps[1][k])
+    bench = _load_bench()
+    from cvpr2020_manet_amd import ops
+    dev = torch.device("cuda", 0)
+    wl = bench.Workload(2, "f32", "f32", dev, n_local=max(K, bench.CONFIGS[2]["T"]))  # bench.py's own n_local at N = 1
+    bank_rows = torch.stack([wl.bank_emb[f] for f in wl.bank_frames]).permute(0, 2, 3, 1).reshape(-1, bench.C)
+    bank_lab = torch.stack([wl.bank_labels[f] for f in wl.bank_frames]).reshape(-1)
+    # step K-1 merges into memory row K-1 (untouched by the one warm-up step): a fresh row of ones; its previous frame is K-2
+    mem = torch.ones(wl.H * wl.W, wl.n_ids, device=dev)
+    cur, prev = wl.frame_emb(K - 1).permute(1, 2, 0), wl.frame_emb(K - 2).permute(1, 2, 0)
+    g = ops.global_match(bank_rows, cur, bank_lab, wl.n_ids, normalize=True, mem=mem)
+    lm = ops.local_match(prev, cur, wl.prev_labs[(K - 1) % 8], wl.n_ids, wl.d)
+    np.testing.assert_array_equal(dumps[0]["global_map"], g.cpu().numpy())
+    np.testing.assert_array_equal(dumps[0]["global_memory"], mem.cpu().numpy())
+    np.testing.assert_array_equal(dumps[0]["local_map"], lm.cpu().numpy())
