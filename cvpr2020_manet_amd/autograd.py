@@ -14,6 +14,8 @@ pointers, so the backward is explicit:
                   backward walks min -> where -> bilinear -> sigmoid -> (x - y)^2 -> avg_pool2d in reverse.
   LocalMatchFullFn  the same with MODEL_LOCAL_DOWNSAMPLE = False (:299-313): raw full-resolution distances, no sigmoid / bilinear.
   CorrelationFn   correlation_package (correlation.py:7-45): forward + manet_correlation_backward_f32.
+  DepthwiseConvFn  the heads' depthwise layers (IntVOS.py:491-493, :537) in training: forward, backward-data and
+                  deterministic backward-weight kernels (csrc/dwconv_train.hip); ops.depthwise_conv2d, IntVOS(train_kernels=True).
 
 `ops.global_match` / `ops.local_match` / `ops.correlation_forward` route here when grad mode is on and an
 embedding requires grad; normalisation and the min-merge with the stored map stay ordinary torch ops on the
@@ -310,3 +312,51 @@ class CorrelationFn(torch.autograd.Function):
                     stride2, ga.data_ptr(), gb.data_ptr(), _stream_ptr(a.device))
         _lib.check(rc, "manet_correlation_backward")
         return ga.to(a0.dtype), gb.to(b0.dtype), None, None, None, None, None
+
+
+class DepthwiseConvFn(torch.autograd.Function):
+    """Depthwise convolution of the heads in training (IntVOS.py:491-493 _split_separable_conv2d.conv1, :537 seperate_conv):
+    F.conv2d(x, weight, bias, padding=K // 2, groups=C) with K = 3 or 7, stride 1, fp32 NCHW.  Forward
+    manet_dwconv_forward_f32; backward manet_dwconv_backward_data_f32 (grad_x) and manet_dwconv_backward_weight_f32 (grad_weight
+    and grad_bias, deterministic) -- each launched only when its gradient is asked for."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from . import ops
+        x = x.contiguous()
+        wt = weight.contiguous()
+        with torch.no_grad():
+            out = ops._dwconv_forward(x, wt, bias)
+        ctx.save_for_backward(x, wt)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        x, wt = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
+        B, C, h, w = x.shape
+        K = wt.shape[-1]
+        dev = x.device
+        g = grad_out.contiguous().float()
+        gx = gw = gb = None
+        with torch.cuda.device(dev):
+            if need_x:
+                gx = torch.empty_like(x)
+                _lib.check(lib.manet_dwconv_backward_data_f32(g.data_ptr(), B, C, h, w, K, wt.data_ptr(), gx.data_ptr(),
+                                                              _stream_ptr(dev)), "manet_dwconv_backward_data_f32")
+            if need_w or need_b:
+                nbytes = ctypes.c_size_t(0)
+                _lib.check(lib.manet_dwconv_backward_weight_workspace_bytes(B, C, h, w, K, ctypes.byref(nbytes)),
+                           "manet_dwconv_backward_weight_workspace_bytes")
+                ws = _scratch(dev, nbytes.value)
+                gw_full = torch.empty_like(wt)
+                gb_full = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
+                _lib.check(lib.manet_dwconv_backward_weight_f32(x.data_ptr(), g.data_ptr(), B, C, h, w, K, gw_full.data_ptr(),
+                                                                None if gb_full is None else gb_full.data_ptr(), ws.data_ptr(),
+                                                                ws.numel(), _stream_ptr(dev)),
+                           "manet_dwconv_backward_weight_f32")
+                gw = gw_full if need_w else None
+                gb = gb_full
+        return gx, gw, gb

@@ -65,6 +65,29 @@ def _pointwise_mode(block=None):
         mode = MFMA_POINTWISE
     return _POINTWISE_MODES[mode]
 
+
+def use_train_kernels(module, on=True):
+    """Training route of the heads' depthwise layers (opt-in, off by default; IntVOS(train_kernels=...) /
+    DynamicSegHead(train_kernels=...) call this): with `on`, every _split_separable_conv2d under `module` (and the embedding
+    head, when `module` is an IntVOS) runs its depthwise convolution on ops.depthwise_conv2d -- HIP forward and backward --
+    whenever it is outside the inference fast path (training mode or grad enabled) on fp32 GPU input.  BN, the 1x1
+    convolutions and the ReLUs stay the framework's modules.  A plain attribute: not a buffer, not in the state dict."""
+    for m in module.modules():
+        if isinstance(m, _split_separable_conv2d) or m is module:
+            object.__setattr__(m, "_train_kernels", bool(on))
+    return module
+
+
+def _train_dw_ok(module, conv, x):
+    """conv (a depthwise Conv2d, K = 3 or 7, stride 1, padding K // 2) runs on ops.depthwise_conv2d: the switch is on, the call is
+    outside the inference fast path (training mode or grad enabled), and input and weight are fp32 on the GPU"""
+    k = conv.kernel_size[0]
+    return (getattr(module, "_train_kernels", False) and (module.training or torch.is_grad_enabled())
+            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.weight.is_cuda
+            and conv.weight.dtype == torch.float32 and conv.kernel_size == (k, k) and k in (3, 7)
+            and conv.stride == (1, 1) and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1)
+            and conv.groups == conv.in_channels == conv.out_channels == x.shape[1] and conv.padding_mode == "zeros")
+
 # arithmetic of the QK^T contraction used by the MODULE-LEVEL functions: "f32" (exact fp32 MFMA) | "bf16" | "bf16x3" |
 # "bf16r".  An IntVOS instance carries its own (constructor argument / cfg.MODEL_MATCH_COMPUTE).
 COMPUTE = "f32"
@@ -301,7 +324,10 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
                 return ops.relu_conv1x1_c1(self._pointwise(x, k, "all", True, False), head[0], head[1])
             return self._pointwise(x, k, "all", True, not defer_relu)
         assert not relu_in and not defer_relu
-        x = self.relu1(self.bn1(self.conv1(x)))
+        if _train_dw_ok(self, self.conv1, x):  # training route (use_train_kernels): the depthwise stage on HIP, fwd + bwd
+            x = self.relu1(self.bn1(ops.depthwise_conv2d(x, self.conv1.weight, self.conv1.bias)))
+        else:
+            x = self.relu1(self.bn1(self.conv1(x)))
         x = self.relu2(self.bn2(self.conv2(x)))
         return x
 
@@ -380,7 +406,8 @@ def _layer1_fused(layer, shared, global_map, local_map, labels, n_ids, size, mem
 
 
 class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
-    def __init__(self, in_dim=None, embed_dim=None, kernel_size=1):
+    def __init__(self, in_dim=None, embed_dim=None, kernel_size=1, train_kernels=False):
+        """train_kernels: the depthwise layers' training route on HIP kernels (use_train_kernels)"""
         super().__init__()
         in_dim = cfg.MODEL_SEMANTIC_EMBEDDING_DIM + 3 if in_dim is None else in_dim
         embed_dim = cfg.MODEL_HEAD_EMBEDDING_DIM if embed_dim is None else embed_dim
@@ -390,6 +417,8 @@ class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
         self.layer4 = _split_separable_conv2d(embed_dim, embed_dim)
         self.conv = nn.Conv2d(embed_dim, 1, 1, 1)
         nn.init.kaiming_normal_(self.conv.weight, mode="fan_out", nonlinearity="relu")
+        if train_kernels:
+            use_train_kernels(self)
 
     def _tail(self, x):
         """layers 2-4 + the 1x1 output conv on the inference fast path; x = layer1's output.  r5: every block's last ReLU
@@ -461,7 +490,8 @@ _EMB_DTYPES = {"f32": torch.float32, "fp32": torch.float32, "float32": torch.flo
 class IntVOS(nn.Module):
     """reference IntVOS.py:530-764: same constructor, methods, dict conventions, state-dict keys."""
 
-    def __init__(self, cfg, feature_extracter, compute=None, emb_dtype=None, pointwise=None, cache_frames=None):
+    def __init__(self, cfg, feature_extracter, compute=None, emb_dtype=None, pointwise=None, cache_frames=None,
+                 train_kernels=None):
         """cfg, feature_extracter: as the reference.  The rest is optional and this implementation's only (default: the
         cfg's MODEL_MATCH_COMPUTE / MODEL_EMB_DTYPE / MODEL_HEAD_POINTWISE / MODEL_CACHE_FRAMES when it has them, else
         "f32" / "f32" / "f32" / True):
@@ -473,7 +503,10 @@ class IntVOS(nn.Module):
                         ~2^-23 per product) | "framework" the framework's GEMM
           cache_frames  keep prepared per-frame operands keyed on the embedding tensor's identity (_prepared_frame).
                         False: every call prepares afresh -- REQUIRED when embeddings are rewritten in place without
-                        torch noticing (HIP-graph replay of the encoder into a static buffer, `.data` writes)"""
+                        torch noticing (HIP-graph replay of the encoder into a static buffer, `.data` writes)
+          train_kernels the depthwise layers of the heads (DynamicSegHead's four blocks, the embedding head's 3x3) on HIP forward /
+                        backward kernels in training mode or with grad enabled (use_train_kernels); default off (cfg's
+                        MODEL_TRAIN_KERNELS when it has it): the framework's grouped convolution, as the reference"""
         super().__init__()
         set_cfg(cfg)
         self.cfg = cfg
@@ -526,6 +559,9 @@ class IntVOS(nn.Module):
         for m in self.modules():  # this model's 1x1 mode (not a process-wide switch: two models may differ)
             if isinstance(m, _split_separable_conv2d):
                 object.__setattr__(m, "_pw_mode", self.pointwise)
+        tk = train_kernels if train_kernels is not None else getattr(cfg, "MODEL_TRAIN_KERNELS", False)
+        self.train_kernels = bool(tk)
+        use_train_kernels(self, self.train_kernels)
 
     def _prepared_bank(self, seq_name, ref_emb_chw, ref_label, ref_emb_hwc, ref_lab_flat, n_ids):
         """The sorted / packed memory bank of the annotated frame, reused while the caller keeps passing the SAME
@@ -889,7 +925,12 @@ class IntVOS(nn.Module):
                     self._store_frame(key, fr)
             self._trim_frames()
             return emb
-        x = self.semantic_embedding(x)
+        if _train_dw_ok(self, self.seperate_conv, x):
+            # training route (use_train_kernels): seperate_conv on the HIP depthwise kernels, the same aliased modules around it
+            x = self.relu1(self.bn1(ops.depthwise_conv2d(x, self.seperate_conv.weight, self.seperate_conv.bias)))
+            x = self.relu2(self.bn2(self.embedding_conv(x)))
+        else:
+            x = self.semantic_embedding(x)
         if x.dtype != self.emb_dtype and not (torch.is_grad_enabled() and x.requires_grad):
             x = x.to(self.emb_dtype)
         if packed:

@@ -870,6 +870,46 @@ def dwconv7x7_bn_relu(x, weight, bias=None, bn=None, relu=True, scale=None, shif
     return out
 
 
+def _dwconv_check(x, weight, bias):
+    _need_gpu(x, "x")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("x must be a float32 [B, C, h, w] tensor")
+    C = x.shape[1]
+    if weight.dim() != 4 or weight.shape[0] != C or weight.shape[1] != 1 or weight.shape[2] != weight.shape[3] \
+            or weight.shape[2] not in (3, 7) or weight.dtype != torch.float32:
+        raise ValueError("weight must be a float32 [C, 1, K, K] tensor with K = 3 or 7 (got %s for C = %d)"
+                         % (tuple(weight.shape), C))
+    if bias is not None and (bias.numel() != C or bias.dtype != torch.float32):
+        raise ValueError("bias must be a float32 [C] tensor")
+    return int(weight.shape[2])
+
+
+def _dwconv_forward(x, weight, bias):
+    """conv + bias on the HIP kernel (manet_dwconv_forward_f32); x, weight contiguous, no autograd"""
+    lib = _lib.load()
+    B, C, h, w = x.shape
+    K = int(weight.shape[2])
+    bz = None if bias is None else bias.detach().contiguous()
+    out = torch.empty_like(x)
+    with _on(x.device):
+        rc = lib.manet_dwconv_forward_f32(x.data_ptr(), B, C, h, w, K, weight.detach().data_ptr(),
+                                          None if bz is None else bz.data_ptr(), out.data_ptr(), _stream_ptr(x.device))
+    _lib.check(rc, "manet_dwconv_forward_f32")
+    return out
+
+
+def depthwise_conv2d(x, weight, bias=None):
+    """F.conv2d(x, weight, bias, padding=K // 2, groups=C) on HIP kernels, differentiable: the heads' depthwise layers in
+    training (IntVOS.py:491-493 _split_separable_conv2d.conv1, 7x7; :537 seperate_conv, 3x3).  x [B, C, h, w] fp32 on the GPU,
+    weight [C, 1, K, K] with K = 3 or 7, bias [C] or None.  With grad wanted the op is autograd.DepthwiseConvFn (forward
+    kernel; backward-data / backward-weight kernels), otherwise the forward kernel alone."""
+    _dwconv_check(x, weight, bias)
+    if _wants_grad(x, weight, bias):
+        from .autograd import DepthwiseConvFn
+        return DepthwiseConvFn.apply(x, weight, bias)
+    return _dwconv_forward(x.contiguous(), weight.contiguous(), bias)
+
+
 PW_COUT = 256  # output channels the MFMA 1x1 kernel is built for (the reference's MODEL_HEAD_EMBEDDING_DIM, config.py:48)
 
 

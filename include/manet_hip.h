@@ -25,6 +25,8 @@
  *                             and correlation_cuda.backward (correlation_cuda.cc:89-167)
  *   manet_upsample_argmax     test.py:253-255 + networks/IntVOS.py:598-599
  *   manet_dwconv7x7_bn_relu_f32  networks/IntVOS.py:491-493,500-502
+ *   manet_dwconv_*_f32        training forward / backward of the heads' depthwise layers: networks/IntVOS.py:491-493
+ *                             (_split_separable_conv2d.conv1) and :537 (seperate_conv)
  *   manet_relu_conv1x1_c1_f32    networks/IntVOS.py:519,525
  *
  * NaN inputs (outside the reference's contract, documented deviation): the global match propagates a NaN
@@ -366,6 +368,24 @@ int manet_dwconv7x7_bn_relu_f32(const float *in, int B, int C, int h, int w, con
 int manet_dwconv7x7_bn_relu_ex(const float *in, int B, int C, int h, int w, const float *weight,
                                const float *bias, const float *bn_scale, const float *bn_shift, int relu,
                                int relu_in, float *out, manet_stream_t stream);
+
+/* Depthwise convolution for training (csrc/dwconv_train.hip): the heads' depthwise layers
+ * _split_separable_conv2d.conv1 (networks/IntVOS.py:491-493: 7x7, padding 3, groups = C) and seperate_conv (:537: 3x3,
+ * padding 1, groups = C).  fp32, NCHW contiguous, stride 1, padding K / 2, K = 3 or 7, any B, C, h, w >= 1.
+ * weight [C][K][K], bias / grad_bias [C].  Invalid arguments (K, non-positive sizes, NULL pointers, a workspace that is too
+ * small) return MANET_E_INVALID before anything is launched.  No allocation, no synchronisation.
+ *   forward:         out = conv(in, weight) + bias (bias NULL: 0); K = 7 is manet_dwconv7x7_bn_relu_ex without BN / ReLU.
+ *   backward-data:   grad_in = the correlation of grad_out with the filter rotated by 180 degrees (zero padding).
+ *   backward-weight: grad_weight[c][t] = sum_{b,y,x} grad_out[b][c][y][x] * in[b][c][y+ty-r][x+tx-r], grad_bias[c] = sum of
+ *                    grad_out[b][c] (grad_bias NULL: not written).  Deterministic: per-(channel, tile, batch slice) sums go to
+ *                    the workspace, a second launch adds them in a fixed order; the bits depend on the shape alone. */
+int manet_dwconv_forward_f32(const float *in, int B, int C, int h, int w, int K, const float *weight, const float *bias,
+                             float *out, manet_stream_t stream);
+int manet_dwconv_backward_data_f32(const float *grad_out, int B, int C, int h, int w, int K, const float *weight,
+                                   float *grad_in, manet_stream_t stream);
+int manet_dwconv_backward_weight_workspace_bytes(int B, int C, int h, int w, int K, size_t *bytes);
+int manet_dwconv_backward_weight_f32(const float *in, const float *grad_out, int B, int C, int h, int w, int K,
+                                     float *grad_weight, float *grad_bias, void *ws, size_t ws_bytes, manet_stream_t stream);
 
 /* DynamicSegHead's output layer, fused (networks/IntVOS.py:519,525: Conv2d(embed_dim, 1, kernel 1) on layer4's ReLU
  * output): out[b][p] = bias[0] + sum_c weight[c] * (relu_in ? max(in[b][c][p], 0) : in[b][c][p]).
