@@ -14,6 +14,7 @@ _i = ctypes.c_int
 _sz = ctypes.c_size_t
 _szp = ctypes.POINTER(ctypes.c_size_t)
 _ip = ctypes.POINTER(ctypes.c_int)
+_f = ctypes.c_float
 
 # name -> (restype, argtypes); must list every symbol of include/manet_hip.h
 SIGNATURES = {
@@ -103,6 +104,14 @@ SIGNATURES = {
     "manet_dwconv_backward_data_f32": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "manet_dwconv_backward_weight_workspace_bytes": (_i, [_i, _i, _i, _i, _i, _szp]),
     "manet_dwconv_backward_weight_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "manet_pw_forward_workspace_bytes": (_i, [_i, _i, _i, _i, _szp]),
+    "manet_pw_forward_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "manet_pw_backward_data_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "manet_pw_backward_weight_workspace_bytes": (_i, [_i, _i, _i, _i, _szp]),
+    "manet_pw_backward_weight_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "manet_bn_relu_workspace_bytes": (_i, [_i, _i, _i, _szp]),
+    "manet_bn_relu_forward_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "manet_bn_relu_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X3, COMPUTE_BF16_REFINE = 0, 1, 2, 3

@@ -16,6 +16,10 @@ pointers, so the backward is explicit:
   CorrelationFn   correlation_package (correlation.py:7-45): forward + manet_correlation_backward_f32.
   DepthwiseConvFn  the heads' depthwise layers (IntVOS.py:491-493, :537) in training: forward, backward-data and
                   deterministic backward-weight kernels (csrc/dwconv_train.hip); ops.depthwise_conv2d, IntVOS(train_kernels=True).
+  PointwiseConvFn  the heads' 1x1 convolutions in training: forward, backward-data and deterministic backward-weight kernels
+                  (csrc/pw_train.hip); ops.pointwise_conv2d, IntVOS(train_kernels="all").
+  BatchNormReluFn  the heads' BatchNorm + ReLU pairs in training (or eval with grad enabled): statistics, running buffers and
+                  the backward on csrc/pw_train.hip's kernels; ops.batch_norm_relu, IntVOS(train_kernels="all").
 
 `ops.global_match` / `ops.local_match` / `ops.correlation_forward` route here when grad mode is on and an
 embedding requires grad; normalisation and the min-merge with the stored map stay ordinary torch ops on the
@@ -360,3 +364,91 @@ class DepthwiseConvFn(torch.autograd.Function):
                 gw = gw_full if need_w else None
                 gb = gb_full
         return gx, gw, gb
+
+
+class PointwiseConvFn(torch.autograd.Function):
+    """1x1 convolution of the heads in training (IntVOS.py:244-332 _split_separable_conv2d.conv2, the embedding head's
+    embedding_conv): F.conv2d(x, weight, bias) with a [Cout, Cin, 1, 1] weight, fp32 NCHW.  Forward manet_pw_forward_f32;
+    backward manet_pw_backward_data_f32 (grad_x) and manet_pw_backward_weight_f32 (grad_weight and / or grad_bias,
+    deterministic) -- each launched only when its gradient is asked for."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from . import ops
+        x = x.contiguous()
+        wt = weight.detach().reshape(weight.shape[0], weight.shape[1]).contiguous()
+        with torch.no_grad():
+            out = ops._pw_forward(x, wt, bias)
+        ctx.save_for_backward(x, wt)
+        ctx.has_bias = bias is not None
+        ctx.wshape = weight.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        x, wt = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
+        from . import ops
+        B, Cin, h, w = x.shape
+        Cout = wt.shape[0]
+        dev = x.device
+        g = grad_out.contiguous().float()
+        gx = gw = gb = None
+        with ops._on(dev):
+            st = _stream_ptr(dev)
+            if need_x:
+                gx = torch.empty_like(x)
+                _lib.check(lib.manet_pw_backward_data_f32(g.data_ptr(), B, Cin, Cout, h * w, wt.data_ptr(), gx.data_ptr(), st),
+                           "manet_pw_backward_data_f32")
+            if need_w or need_b:
+                nbytes = ops._ws_bytes("manet_pw_backward_weight_workspace_bytes", B, Cin, Cout, h * w)
+                ws = ops._workspace(dev, "pw_backward_weight", nbytes)
+                gw = torch.empty(ctx.wshape, dtype=torch.float32, device=dev) if need_w else None
+                gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if need_b else None
+                _lib.check(lib.manet_pw_backward_weight_f32(x.data_ptr(), g.data_ptr(), B, Cin, Cout, h * w,
+                                                            None if gw is None else gw.data_ptr(),
+                                                            None if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, st),
+                           "manet_pw_backward_weight_f32")
+        return gx, gw, gb
+
+
+class BatchNormReluFn(torch.autograd.Function):
+    """relu(batch_norm(x)) of the heads (IntVOS.py:244-332 bn1 -> relu1, bn2 -> relu2; the embedding head's), fp32 NCHW.
+    Forward manet_bn_relu_forward_f32 (training: batch statistics, running_mean / running_var updated in place; eval: the
+    running statistics); saves x and the per-channel mean / invstd it used, as the framework does.  Backward
+    manet_bn_relu_backward_f32, asked only for the gradients needed (grad_x; grad_weight / grad_bias)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, training):
+        from . import ops
+        x = x.contiguous()
+        with torch.no_grad():
+            out, save = ops._bn_relu_forward(x, weight, bias, running_mean, running_var, momentum, eps, training)
+        ctx.save_for_backward(x, weight, bias, save)
+        ctx.training = bool(training)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        x, weight, bias, save = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        B, C, h, w = x.shape
+        dev = x.device
+        g = grad_out.contiguous().float()
+        gx = torch.empty_like(x) if need_x else None
+        gw = torch.empty((C,), dtype=torch.float32, device=dev) if need_w else None
+        gb = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
+        if gx is None and gw is None and gb is None:
+            return None, None, None, None, None, None, None, None
+        from . import ops
+        with ops._on(dev):
+            nbytes = ops._ws_bytes("manet_bn_relu_workspace_bytes", B, C, h * w)
+            ws = ops._workspace(dev, "bn_relu", nbytes)
+            _lib.check(lib.manet_bn_relu_backward_f32(g.data_ptr(), x.data_ptr(), B, C, h * w, weight.data_ptr(), bias.data_ptr(),
+                                                      save.data_ptr(), save.data_ptr() + 4 * C, 1 if ctx.training else 0,
+                                                      None if gx is None else gx.data_ptr(), None if gw is None else gw.data_ptr(),
+                                                      None if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(dev)),
+                       "manet_bn_relu_backward_f32")
+        return gx, gw, gb, None, None, None, None, None

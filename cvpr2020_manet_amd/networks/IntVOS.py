@@ -66,15 +66,24 @@ def _pointwise_mode(block=None):
     return _POINTWISE_MODES[mode]
 
 
+def _train_mode(on):
+    """the switch's value: "all" (depthwise, BatchNorm + ReLU and the 1x1 convolutions), else bool(on) (True: the depthwise
+    layers)"""
+    return "all" if isinstance(on, str) and on.lower() == "all" else bool(on)
+
+
 def use_train_kernels(module, on=True):
-    """Training route of the heads' depthwise layers (opt-in, off by default; IntVOS(train_kernels=...) /
-    DynamicSegHead(train_kernels=...) call this): with `on`, every _split_separable_conv2d under `module` (and the embedding
-    head, when `module` is an IntVOS) runs its depthwise convolution on ops.depthwise_conv2d -- HIP forward and backward --
-    whenever it is outside the inference fast path (training mode or grad enabled) on fp32 GPU input.  BN, the 1x1
-    convolutions and the ReLUs stay the framework's modules.  A plain attribute: not a buffer, not in the state dict."""
+    """Training route of the heads on HIP kernels (opt-in, off by default; IntVOS(train_kernels=...) /
+    DynamicSegHead(train_kernels=...) call this).  With `on` True, every _split_separable_conv2d under `module` (and the
+    embedding head, when `module` is an IntVOS) runs its depthwise convolution on ops.depthwise_conv2d -- HIP forward and
+    backward -- whenever it is outside the inference fast path (training mode or grad enabled) on fp32 GPU input; BN, the 1x1
+    convolutions and the ReLUs stay the framework's modules.  With on = "all" the BatchNorm + ReLU pairs run on
+    ops.batch_norm_relu and the 1x1 convolutions on ops.pointwise_conv2d as well (a BatchNorm without affine parameters,
+    running statistics or a numeric momentum keeps the stock modules).  A plain attribute: not a buffer, not in the state dict."""
+    mode = _train_mode(on)
     for m in module.modules():
         if isinstance(m, _split_separable_conv2d) or m is module:
-            object.__setattr__(m, "_train_kernels", bool(on))
+            object.__setattr__(m, "_train_kernels", mode)
     return module
 
 
@@ -87,6 +96,28 @@ def _train_dw_ok(module, conv, x):
             and conv.weight.dtype == torch.float32 and conv.kernel_size == (k, k) and k in (3, 7)
             and conv.stride == (1, 1) and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1)
             and conv.groups == conv.in_channels == conv.out_channels == x.shape[1] and conv.padding_mode == "zeros")
+
+def _train_all(module, x):
+    """the "all" route applies: switch "all", outside the inference fast path, fp32 GPU input"""
+    return (getattr(module, "_train_kernels", False) == "all" and (module.training or torch.is_grad_enabled())
+            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4)
+
+
+def _train_bn_relu(bn, x):
+    """relu(bn(x)) of the "all" route: ops.batch_norm_relu, or the stock modules for a BatchNorm it does not take"""
+    if ops.batch_norm_relu_ok(bn) and all(t.is_cuda and t.dtype == torch.float32 for t in (bn.weight, bn.bias, bn.running_mean,
+                                                                                          bn.running_var)):
+        return ops.batch_norm_relu(x, bn)
+    return F.relu(bn(x))
+
+
+def _train_pw(conv, x):
+    """conv(x) of the "all" route: ops.pointwise_conv2d for a plain 1x1 convolution with fp32 GPU weights, else the module"""
+    if (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.weight.is_cuda and conv.weight.dtype == torch.float32):
+        return ops.pointwise_conv2d(x, conv.weight, conv.bias)
+    return conv(x)
+
 
 # arithmetic of the QK^T contraction used by the MODULE-LEVEL functions: "f32" (exact fp32 MFMA) | "bf16" | "bf16x3" |
 # "bf16r".  An IntVOS instance carries its own (constructor argument / cfg.MODEL_MATCH_COMPUTE).
@@ -324,6 +355,10 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
                 return ops.relu_conv1x1_c1(self._pointwise(x, k, "all", True, False), head[0], head[1])
             return self._pointwise(x, k, "all", True, not defer_relu)
         assert not relu_in and not defer_relu
+        if _train_all(self, x):  # training route "all" (use_train_kernels): the whole block on HIP, fwd + bwd
+            x = ops.depthwise_conv2d(x, self.conv1.weight, self.conv1.bias) if _train_dw_ok(self, self.conv1, x) else self.conv1(x)
+            x = _train_pw(self.conv2, _train_bn_relu(self.bn1, x))
+            return _train_bn_relu(self.bn2, x)
         if _train_dw_ok(self, self.conv1, x):  # training route (use_train_kernels): the depthwise stage on HIP, fwd + bwd
             x = self.relu1(self.bn1(ops.depthwise_conv2d(x, self.conv1.weight, self.conv1.bias)))
         else:
@@ -407,7 +442,8 @@ def _layer1_fused(layer, shared, global_map, local_map, labels, n_ids, size, mem
 
 class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
     def __init__(self, in_dim=None, embed_dim=None, kernel_size=1, train_kernels=False):
-        """train_kernels: the depthwise layers' training route on HIP kernels (use_train_kernels)"""
+        """train_kernels: the training route on HIP kernels (use_train_kernels): True the depthwise layers, "all" every
+        layer of the blocks"""
         super().__init__()
         in_dim = cfg.MODEL_SEMANTIC_EMBEDDING_DIM + 3 if in_dim is None else in_dim
         embed_dim = cfg.MODEL_HEAD_EMBEDDING_DIM if embed_dim is None else embed_dim
@@ -417,8 +453,8 @@ class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
         self.layer4 = _split_separable_conv2d(embed_dim, embed_dim)
         self.conv = nn.Conv2d(embed_dim, 1, 1, 1)
         nn.init.kaiming_normal_(self.conv.weight, mode="fan_out", nonlinearity="relu")
-        if train_kernels:
-            use_train_kernels(self)
+        if _train_mode(train_kernels):
+            use_train_kernels(self, train_kernels)
 
     def _tail(self, x):
         """layers 2-4 + the 1x1 output conv on the inference fast path; x = layer1's output.  r5: every block's last ReLU
@@ -505,8 +541,9 @@ class IntVOS(nn.Module):
                         False: every call prepares afresh -- REQUIRED when embeddings are rewritten in place without
                         torch noticing (HIP-graph replay of the encoder into a static buffer, `.data` writes)
           train_kernels the depthwise layers of the heads (DynamicSegHead's four blocks, the embedding head's 3x3) on HIP forward /
-                        backward kernels in training mode or with grad enabled (use_train_kernels); default off (cfg's
-                        MODEL_TRAIN_KERNELS when it has it): the framework's grouped convolution, as the reference"""
+                        backward kernels in training mode or with grad enabled (use_train_kernels); "all": their BatchNorm +
+                        ReLU pairs and 1x1 convolutions too; default off (cfg's MODEL_TRAIN_KERNELS when it has it): the
+                        framework's modules, as the reference"""
         super().__init__()
         set_cfg(cfg)
         self.cfg = cfg
@@ -560,7 +597,7 @@ class IntVOS(nn.Module):
             if isinstance(m, _split_separable_conv2d):
                 object.__setattr__(m, "_pw_mode", self.pointwise)
         tk = train_kernels if train_kernels is not None else getattr(cfg, "MODEL_TRAIN_KERNELS", False)
-        self.train_kernels = bool(tk)
+        self.train_kernels = _train_mode(tk)
         use_train_kernels(self, self.train_kernels)
 
     def _prepared_bank(self, seq_name, ref_emb_chw, ref_label, ref_emb_hwc, ref_lab_flat, n_ids):
@@ -925,7 +962,15 @@ class IntVOS(nn.Module):
                     self._store_frame(key, fr)
             self._trim_frames()
             return emb
-        if _train_dw_ok(self, self.seperate_conv, x):
+        if _train_all(self, x):
+            # training route "all" (use_train_kernels): the whole embedding head on HIP, the same aliased modules' parameters
+            if _train_dw_ok(self, self.seperate_conv, x):
+                x = ops.depthwise_conv2d(x, self.seperate_conv.weight, self.seperate_conv.bias)
+            else:
+                x = self.seperate_conv(x)
+            x = _train_pw(self.embedding_conv, _train_bn_relu(self.bn1, x))
+            x = _train_bn_relu(self.bn2, x)
+        elif _train_dw_ok(self, self.seperate_conv, x):
             # training route (use_train_kernels): seperate_conv on the HIP depthwise kernels, the same aliased modules around it
             x = self.relu1(self.bn1(ops.depthwise_conv2d(x, self.seperate_conv.weight, self.seperate_conv.bias)))
             x = self.relu2(self.bn2(self.embedding_conv(x)))

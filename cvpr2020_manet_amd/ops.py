@@ -5,6 +5,9 @@ below hands raw device pointers, element strides and that stream to libmanet_hip
 must live on a HIP device -- there is deliberately no CPU path (a silent fallback would void the
 parity claims); CPU tensors raise.
 """
+import ctypes
+import functools
+
 import torch
 
 from . import _lib
@@ -908,6 +911,106 @@ def depthwise_conv2d(x, weight, bias=None):
         from .autograd import DepthwiseConvFn
         return DepthwiseConvFn.apply(x, weight, bias)
     return _dwconv_forward(x.contiguous(), weight.contiguous(), bias)
+
+
+def _pw_check(x, weight, bias):
+    _need_gpu(x, "x")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("x must be a float32 [B, Cin, h, w] tensor")
+    Cin = x.shape[1]
+    if weight.dim() != 4 or weight.shape[1] != Cin or weight.shape[2:] != (1, 1) or weight.dtype != torch.float32:
+        raise ValueError("weight must be a float32 [Cout, Cin, 1, 1] tensor (got %s for Cin = %d)" % (tuple(weight.shape), Cin))
+    if bias is not None and (bias.numel() != weight.shape[0] or bias.dtype != torch.float32):
+        raise ValueError("bias must be a float32 [Cout] tensor")
+
+
+@functools.lru_cache(maxsize=256)
+def _ws_bytes(query, *dims):
+    """size of a workspace query of the C ABI (manet_*_workspace_bytes), per shape: a function of the shape alone"""
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(getattr(_lib.load(), query)(*dims, ctypes.byref(nbytes)), query)
+    return nbytes.value
+
+
+def _pw_forward(x, weight, bias):
+    """W x + bias on the HIP kernels (manet_pw_forward_f32); x, weight contiguous, no autograd"""
+    lib = _lib.load()
+    B, Cin, h, w = x.shape
+    Cout = int(weight.shape[0])
+    bz = None if bias is None else bias.detach().contiguous()
+    out = torch.empty((B, Cout, h, w), dtype=torch.float32, device=x.device)
+    nbytes = _ws_bytes("manet_pw_forward_workspace_bytes", B, Cin, Cout, h * w)
+    with _on(x.device):
+        ws = _workspace(x.device, "pw_forward", nbytes) if nbytes else None
+        rc = lib.manet_pw_forward_f32(x.data_ptr(), B, Cin, Cout, h * w, weight.detach().data_ptr(),
+                                      None if bz is None else bz.data_ptr(), out.data_ptr(),
+                                      None if ws is None else ws.data_ptr(), nbytes, _stream_ptr(x.device))
+    _lib.check(rc, "manet_pw_forward_f32")
+    return out
+
+
+def pointwise_conv2d(x, weight, bias=None):
+    """F.conv2d(x, weight, bias) for a 1x1 kernel on HIP kernels, differentiable: the heads' 1x1 convolutions in training
+    (IntVOS.py:244-332 _split_separable_conv2d.conv2, the embedding head's embedding_conv).  x [B, Cin, h, w] fp32 on the GPU
+    (any strides), weight [Cout, Cin, 1, 1], bias [Cout] or None.  With grad wanted the op is autograd.PointwiseConvFn (forward
+    kernel; backward-data / backward-weight kernels), otherwise the forward kernel alone."""
+    _pw_check(x, weight, bias)
+    if _wants_grad(x, weight, bias):
+        from .autograd import PointwiseConvFn
+        return PointwiseConvFn.apply(x, weight, bias)
+    return _pw_forward(x.contiguous(), weight.contiguous(), bias)
+
+
+def batch_norm_relu_ok(bn):
+    """bn is a BatchNorm2d batch_norm_relu takes: affine, tracking running statistics, a numeric momentum"""
+    return (isinstance(bn, torch.nn.BatchNorm2d) and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and bn.running_mean is not None and bn.running_var is not None)
+
+
+def _bn_relu_forward(x, weight, bias, running_mean, running_var, momentum, eps, training):
+    """(out, save) of relu(batch_norm(x)) on the HIP kernels (manet_bn_relu_forward_f32), save [2, C] = the mean and invstd
+    used; x contiguous"""
+    lib = _lib.load()
+    B, C, h, w = x.shape
+    dev = x.device
+    out = torch.empty_like(x)
+    save = torch.empty((2, C), dtype=torch.float32, device=dev)
+    nbytes = _ws_bytes("manet_bn_relu_workspace_bytes", B, C, h * w)
+    with _on(dev):
+        ws = _workspace(dev, "bn_relu", nbytes)
+        sp = save.data_ptr()
+        rc = lib.manet_bn_relu_forward_f32(x.data_ptr(), B, C, h * w, weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
+                                           running_var.data_ptr(), float(momentum), float(eps), 1 if training else 0, out.data_ptr(),
+                                           sp, sp + 4 * C, ws.data_ptr(), nbytes, _stream_ptr(dev))
+    _lib.check(rc, "manet_bn_relu_forward_f32")
+    return out, save
+
+
+def batch_norm_relu(x, bn):
+    """relu(bn(x)) on HIP kernels, differentiable: the heads' BatchNorm + ReLU pairs in training (IntVOS.py:244-332 bn1 -> relu1,
+    bn2 -> relu2; the embedding head's).  x [B, C, h, w] fp32 on the GPU; bn an nn.BatchNorm2d with affine parameters, running
+    statistics and a numeric momentum (batch_norm_relu_ok) whose parameters and buffers are fp32 on x's device.  bn.training
+    selects batch statistics -- running_mean / running_var / num_batches_tracked updated as nn.BatchNorm2d does -- or the
+    running ones.  With grad wanted the op is autograd.BatchNormReluFn, otherwise the forward kernels alone."""
+    _need_gpu(x, "x")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("x must be a float32 [B, C, h, w] tensor")
+    if not batch_norm_relu_ok(bn):
+        raise ValueError("batch_norm_relu needs an affine BatchNorm2d with running statistics and a numeric momentum")
+    C = x.shape[1]
+    for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+        if t.numel() != C or t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous():
+            raise ValueError("bn's parameters and running statistics must be contiguous fp32 [C] tensors on x's device")
+    if bn.training:
+        size = x.shape[0] * x.shape[2] * x.shape[3]
+        if size == 1:  # nn.BatchNorm2d's own check (F.batch_norm -> _verify_batch_size)
+            raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(x.size()))
+        bn.num_batches_tracked.add_(1)
+    if _wants_grad(x, bn.weight, bn.bias):
+        from .autograd import BatchNormReluFn
+        return BatchNormReluFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, bn.training)
+    return _bn_relu_forward(x.contiguous(), bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
+                            bn.training)[0]
 
 
 PW_COUT = 256  # output channels the MFMA 1x1 kernel is built for (the reference's MODEL_HEAD_EMBEDDING_DIM, config.py:48)

@@ -27,6 +27,8 @@
  *   manet_dwconv7x7_bn_relu_f32  networks/IntVOS.py:491-493,500-502
  *   manet_dwconv_*_f32        training forward / backward of the heads' depthwise layers: networks/IntVOS.py:491-493
  *                             (_split_separable_conv2d.conv1) and :537 (seperate_conv)
+ *   manet_pw_*_f32, manet_bn_relu_*_f32  training forward / backward of the heads' 1x1 convolutions and BatchNorm + ReLU:
+ *                             networks/IntVOS.py:244-332 and the embedding head's tail
  *   manet_relu_conv1x1_c1_f32    networks/IntVOS.py:519,525
  *
  * NaN inputs (outside the reference's contract, documented deviation): the global match propagates a NaN
@@ -386,6 +388,41 @@ int manet_dwconv_backward_data_f32(const float *grad_out, int B, int C, int h, i
 int manet_dwconv_backward_weight_workspace_bytes(int B, int C, int h, int w, int K, size_t *bytes);
 int manet_dwconv_backward_weight_f32(const float *in, const float *grad_out, int B, int C, int h, int w, int K,
                                      float *grad_weight, float *grad_bias, void *ws, size_t ws_bytes, manet_stream_t stream);
+
+/* 1x1 convolution and BatchNorm + ReLU for training (csrc/pw_train.hip): the rest of a head block,
+ * networks/IntVOS.py:244-332 (_split_separable_conv2d: bn1 -> relu1 -> conv2 -> bn2 -> relu2) and the embedding head's tail.
+ * fp32, NCHW contiguous, stride 1, any B, Cin, Cout, C, HW >= 1.  weight / grad_weight [Cout][Cin], bias / grad_bias [Cout].
+ * Invalid arguments (non-positive sizes, NULL pointers, a workspace that is too small, one value per channel in training)
+ * return MANET_E_INVALID before anything is launched.  No allocation, no synchronisation, no atomics: every result depends
+ * on the shape alone, bit for bit.
+ *   pw forward:         out = W x + bias (bias NULL: 0).  Cout = 256 with HW % 4 == 0 runs manet_conv1x1_f32 on W
+ *                       transposed into `ws` (manet_pw_forward_workspace_bytes; 0 bytes otherwise, ws may be NULL).
+ *   pw backward-data:   grad_in = W^T grad_out.
+ *   pw backward-weight: grad_weight = sum_{b,p} grad_out x^T, grad_bias = sum_{b,p} grad_out (either may be NULL, not both):
+ *                       per-(tile, pixel slice) slabs in the workspace, added in a fixed order by a second launch.
+ *   bn_relu forward:    out = max((in - mean) * invstd * gamma + beta, 0).  training != 0: batch statistics (biased
+ *                       variance), running_mean / running_var (may be NULL) updated with `momentum` and the unbiased
+ *                       variance as nn.BatchNorm2d; training == 0: the running statistics, nothing updated.  save_mean /
+ *                       save_invstd [C] receive the statistics used (the backward's input).
+ *   bn_relu backward:   g = grad_out * [out > 0]; grad_beta = sum g, grad_gamma = sum g * xhat, grad_in =
+ *                       gamma * invstd * (g - grad_beta / n - xhat * grad_gamma / n) (training) or gamma * invstd * g (eval);
+ *                       any of the three may be NULL and is then not computed.
+ *   manet_bn_relu_workspace_bytes covers both bn_relu calls. */
+int manet_pw_forward_workspace_bytes(int B, int Cin, int Cout, int HW, size_t *bytes);
+int manet_pw_forward_f32(const float *in, int B, int Cin, int Cout, int HW, const float *weight, const float *bias, float *out,
+                         void *ws, size_t ws_bytes, manet_stream_t stream);
+int manet_pw_backward_data_f32(const float *grad_out, int B, int Cin, int Cout, int HW, const float *weight, float *grad_in,
+                               manet_stream_t stream);
+int manet_pw_backward_weight_workspace_bytes(int B, int Cin, int Cout, int HW, size_t *bytes);
+int manet_pw_backward_weight_f32(const float *in, const float *grad_out, int B, int Cin, int Cout, int HW, float *grad_weight,
+                                 float *grad_bias, void *ws, size_t ws_bytes, manet_stream_t stream);
+int manet_bn_relu_workspace_bytes(int B, int C, int HW, size_t *bytes);
+int manet_bn_relu_forward_f32(const float *in, int B, int C, int HW, const float *gamma, const float *beta, float *running_mean,
+                              float *running_var, float momentum, float eps, int training, float *out, float *save_mean,
+                              float *save_invstd, void *ws, size_t ws_bytes, manet_stream_t stream);
+int manet_bn_relu_backward_f32(const float *grad_out, const float *in, int B, int C, int HW, const float *gamma, const float *beta,
+                               const float *save_mean, const float *save_invstd, int training, float *grad_in, float *grad_gamma,
+                               float *grad_beta, void *ws, size_t ws_bytes, manet_stream_t stream);
 
 /* DynamicSegHead's output layer, fused (networks/IntVOS.py:519,525: Conv2d(embed_dim, 1, kernel 1) on layer4's ReLU
  * output): out[b][p] = bias[0] + sum_c weight[c] * (relu_in ? max(in[b][c][p], 0) : in[b][c][p]).
