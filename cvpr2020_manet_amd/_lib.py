@@ -112,6 +112,12 @@ SIGNATURES = {
     "manet_bn_relu_workspace_bytes": (_i, [_i, _i, _i, _szp]),
     "manet_bn_relu_forward_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "manet_bn_relu_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "manet_loss_ce_topk_workspace_bytes": (_i, [_i, _i, _i, _szp]),
+    "manet_loss_ce_pixels_f32": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "manet_loss_ce_topk_forward_f32": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i64, _f,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "manet_loss_ce_topk_backward_f32": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i64, _f,
+                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X3, COMPUTE_BF16_REFINE = 0, 1, 2, 3

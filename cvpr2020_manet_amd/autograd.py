@@ -20,6 +20,9 @@ pointers, so the backward is explicit:
                   (csrc/pw_train.hip); ops.pointwise_conv2d, IntVOS(train_kernels="all").
   BatchNormReluFn  the heads' BatchNorm + ReLU pairs in training (or eval with grad enabled): statistics, running buffers and
                   the backward on csrc/pw_train.hip's kernels; ops.batch_norm_relu, IntVOS(train_kernels="all").
+  UpsampledCrossEntropyTopKFn  the loss behind the head (train_stage1.py:126-153, networks/loss.py:44-81): bilinear upsample,
+                  cross-entropy, hard-pixel top-k and mean as one op, deterministic forward and backward (csrc/loss_train.hip);
+                  ops.upsampled_cross_entropy_topk, networks.loss.Added_CrossEntropyLoss.
 
 `ops.global_match` / `ops.local_match` / `ops.correlation_forward` route here when grad mode is on and an
 embedding requires grad; normalisation and the min-merge with the stored map stay ordinary torch ops on the
@@ -452,3 +455,40 @@ class BatchNormReluFn(torch.autograd.Function):
                                                       None if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(dev)),
                        "manet_bn_relu_backward_f32")
         return gx, gw, gb, None, None, None, None, None
+
+
+class UpsampledCrossEntropyTopKFn(torch.autograd.Function):
+    """The loss behind the head (train_stage1.py:126-153 + networks/loss.py:44-81: bilinear upsample, cross-entropy with
+    ignore_index=255, top-k of the pixel losses, mean) as one op on csrc/loss_train.hip's kernels; ops.upsampled_cross_entropy_topk,
+    networks.loss.Added_CrossEntropyLoss.  Forward manet_loss_ce_topk_forward_f32; it keeps the pixel losses and each row's
+    threshold (t, n_gt, n_eq), from which manet_loss_ce_topk_backward_f32 -- launched only when `logits` wants its gradient --
+    gathers d logits in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, size, k, divisor):
+        from . import ops
+        logits = logits.detach()
+        with torch.no_grad():
+            loss, pix, stats = ops._loss_forward(logits, labels, size, k, divisor)
+        ctx.save_for_backward(logits, labels, pix, stats)
+        ctx.size, ctx.k, ctx.divisor = size, k, divisor
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        from . import ops
+        logits, labels, pix, stats = ctx.saved_tensors
+        dev = logits.device
+        B = logits.shape[0]
+        g = grad_out.detach()
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            g = g.float().contiguous()
+        gl = torch.empty(logits.shape, dtype=torch.float32, device=dev)
+        with ops._on(dev):
+            rc = _lib.load().manet_loss_ce_topk_backward_f32(*ops._loss_args(logits, labels, ctx.size), ctx.k, ctx.divisor,
+                                                             pix.data_ptr(), stats.data_ptr(), stats.data_ptr() + 4 * B,
+                                                             stats.data_ptr() + 8 * B, g.data_ptr(), gl.data_ptr(), _stream_ptr(dev))
+        _lib.check(rc, "manet_loss_ce_topk_backward_f32")
+        return gl, None, None, None, None

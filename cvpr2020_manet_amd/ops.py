@@ -1167,3 +1167,88 @@ def relu_conv1x1_c1(x, weight, bias=None, relu_in=True):
                                            int(bool(relu_in)), out.data_ptr(), _stream_ptr(x.device))
     _lib.check(rc, "manet_relu_conv1x1_c1_f32")
     return out
+
+
+_LOSS_LABEL_DTYPES = (torch.int64, torch.int32, torch.uint8)
+LOSS_MAX_CHANNELS = 64  # MANET_MAX_IDS
+
+
+def upsampled_cross_entropy_ok(logits, labels, size=None):
+    """the fused loss takes these: fp32 [B, C <= 64, h, w] logits and int64 / int32 / uint8 [B, H, W] labels on one HIP device, with
+    (H, W) = `size` (default: the logits' own) no smaller than (h, w)"""
+    if not (isinstance(logits, torch.Tensor) and isinstance(labels, torch.Tensor) and logits.is_cuda and labels.is_cuda):
+        return False
+    if logits.device != labels.device or logits.dtype != torch.float32 or labels.dtype not in _LOSS_LABEL_DTYPES:
+        return False
+    if logits.dim() != 4 or labels.dim() != 3 or logits.numel() == 0 or not 1 <= logits.shape[1] <= LOSS_MAX_CHANNELS:
+        return False
+    H, W = (int(size[0]), int(size[1])) if size is not None else (logits.shape[2], logits.shape[3])
+    return (tuple(labels.shape) == (logits.shape[0], H, W) and logits.shape[2] <= H <= 16384 and logits.shape[3] <= W <= 16384)
+
+
+def _loss_args(logits, labels, size):
+    """the leading arguments every manet_loss_ce_* call shares: pointers, element strides, label element size, dimensions"""
+    if not upsampled_cross_entropy_ok(logits, labels, size):
+        _need_gpu(logits, "logits")
+        _need_gpu(labels, "labels")
+        raise ValueError("upsampled cross-entropy: logits must be float32 [B, C <= %d, h, w], labels int64 / int32 / uint8 [B, H, W] with "
+                         "(H, W) = size >= (h, w) on the same device (got %s %s, %s %s, size %s)"
+                         % (LOSS_MAX_CHANNELS, tuple(logits.shape), logits.dtype, tuple(labels.shape), labels.dtype, size))
+    B, C, h, w = logits.shape
+    H, W = int(size[0]), int(size[1])
+    return (logits.data_ptr(), logits.stride(0), logits.stride(1), logits.stride(2), logits.stride(3), labels.data_ptr(),
+            labels.element_size(), labels.stride(0), labels.stride(1), labels.stride(2), B, C, h, w, H, W)
+
+
+def upsampled_cross_entropy_pixels(logits, labels, size):
+    """F.cross_entropy(F.interpolate(logits, size, mode='bilinear', align_corners=True), labels, ignore_index=255,
+    reduction='none') as [B, H*W], in one launch that never writes the upsampled logits (manet_loss_ce_pixels_f32).  No backward:
+    the differentiable op is upsampled_cross_entropy_topk."""
+    _refuse_autograd("upsampled_cross_entropy_pixels", logits)
+    logits, labels = logits.detach(), labels.detach()
+    args = _loss_args(logits, labels, size)
+    out = torch.empty((logits.shape[0], int(size[0]) * int(size[1])), dtype=torch.float32, device=logits.device)
+    with _on(logits.device):
+        rc = _lib.load().manet_loss_ce_pixels_f32(*args, out.data_ptr(), _stream_ptr(logits.device))
+    _lib.check(rc, "manet_loss_ce_pixels_f32")
+    return out
+
+
+def _loss_forward(logits, labels, size, k, divisor):
+    """manet_loss_ce_topk_forward_f32 -> (loss [], pixel_losses [B, H*W], stats int32 [3, B] = (bits of t, n_gt, n_eq))"""
+    args = _loss_args(logits, labels, size)
+    dev = logits.device
+    B, H, W = logits.shape[0], int(size[0]), int(size[1])
+    pix = torch.empty((B, H * W), dtype=torch.float32, device=dev)
+    stats = torch.empty((3, B), dtype=torch.int32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    nbytes = _ws_bytes("manet_loss_ce_topk_workspace_bytes", B, H, W)
+    with _on(dev):
+        ws = _workspace(dev, "loss_ce_topk", nbytes)
+        rc = _lib.load().manet_loss_ce_topk_forward_f32(*args, int(k), float(divisor), pix.data_ptr(), loss.data_ptr(), stats.data_ptr(),
+                                                        stats.data_ptr() + 4 * B, stats.data_ptr() + 8 * B, ws.data_ptr(), nbytes,
+                                                        _stream_ptr(dev))
+    _lib.check(rc, "manet_loss_ce_topk_forward_f32")
+    return loss, pix, stats
+
+
+def upsampled_cross_entropy_topk(logits, labels, size, k, divisor=None, return_stats=False):
+    """The training loss behind the head as one differentiable op (train_stage1.py:126-153 + networks/loss.py:44-81):
+    mean(topk(cross_entropy(interpolate(logits, size, bilinear, align_corners=True), labels, ignore_index=255, 'none'), k, dim=1)).
+    logits [B, C, h, w] fp32 (any strides), labels [B, H, W] int64 / int32 / uint8, size = (H, W), 1 <= k <= H * W; the sum of the
+    selected losses is divided by `divisor` (default B * k: the reference's mean).  Returns a scalar.  With grad wanted for
+    `logits` the op is autograd.UpsampledCrossEntropyTopKFn, otherwise the forward kernels alone.  Ties at the k-th loss share the
+    remaining weight equally; see include/manet_hip.h.
+    return_stats (no autograd): (loss, pixel_losses [B, H*W], t [B] = each row's k-th largest loss, n_gt [B] = #{loss > t},
+    n_eq [B] = #{loss == t})."""
+    k = int(k)
+    if divisor is None:
+        divisor = float(logits.shape[0] * k)
+    if return_stats:
+        _refuse_autograd("upsampled_cross_entropy_topk(return_stats=True)", logits)
+        loss, pix, stats = _loss_forward(logits.detach(), labels, size, k, divisor)
+        return loss, pix, stats[0].view(torch.float32), stats[1], stats[2]
+    if _wants_grad(logits):
+        from .autograd import UpsampledCrossEntropyTopKFn
+        return UpsampledCrossEntropyTopKFn.apply(logits, labels, (int(size[0]), int(size[1])), k, float(divisor))
+    return _loss_forward(logits.detach(), labels, size, k, divisor)[0]

@@ -29,12 +29,19 @@
  *                             (_split_separable_conv2d.conv1) and :537 (seperate_conv)
  *   manet_pw_*_f32, manet_bn_relu_*_f32  training forward / backward of the heads' 1x1 convolutions and BatchNorm + ReLU:
  *                             networks/IntVOS.py:244-332 and the embedding head's tail
+ *   manet_loss_ce_*_f32       the training loss behind the head, fused: train_stage1.py:126-153 + networks/loss.py:44-81
+ *                             (bilinear upsample + cross-entropy + hard-pixel top-k + mean, forward and backward)
  *   manet_relu_conv1x1_c1_f32    networks/IntVOS.py:519,525
  *
  * NaN inputs (outside the reference's contract, documented deviation): the global match propagates a NaN
  * distance to the output like torch.min does, but a NaN bank row poisons only its own object (in the reference
  * the +1e20 label mask spreads it to every object); the local masked min (fminf) and the mask-step argmax ignore
- * NaN candidates where torch.min / torch.argmax would return them.
+ * NaN candidates where torch.min / torch.argmax would return them.  The fused training loss (manet_loss_ce_*): a NaN
+ * logit makes the loss of the pixels it taps NaN, which orders above every finite loss as in torch.topk, so it is always
+ * among the top k: the scalar is NaN and so is the gradient at its taps.
+ * Ties (the fused training loss): pixels whose loss exceeds the k-th largest loss t have weight 1, the n_eq pixels whose
+ * loss equals t each (k - n_gt) / n_eq.  The loss value is torch.topk's; the gradient is a sub-gradient that depends on
+ * no order (torch.topk keeps k - n_gt of the tied pixels by its own traversal) and is the reference's when nothing ties.
  *
  * Status codes: 0 = ok; negative = error (see MANET_E_*); manet_last_error_string() gives the
  * text of the last error raised on the calling thread.
@@ -423,6 +430,47 @@ int manet_bn_relu_forward_f32(const float *in, int B, int C, int HW, const float
 int manet_bn_relu_backward_f32(const float *grad_out, const float *in, int B, int C, int HW, const float *gamma, const float *beta,
                                const float *save_mean, const float *save_invstd, int training, float *grad_in, float *grad_gamma,
                                float *grad_beta, void *ws, size_t ws_bytes, manet_stream_t stream);
+
+/* The training loss behind the head, fused (csrc/loss_train.hip): train_stage1.py:126-153 + networks/loss.py:44-81, i.e.
+ *   F.interpolate(logits, (H, W), 'bilinear', align_corners=True) -> CrossEntropyLoss(ignore_index=255, reduction='none')
+ *   -> torch.topk(pixel_losses, k, dim=1) -> mean, and its backward.
+ * logits [B][C][h][w] fp32 with element strides (l_sb, l_sc, l_sy, l_sx), 1 <= C <= 64; labels [B][H][W] with element strides
+ * (y_sb, y_sy, y_sx) and label_elem_size 8 (int64), 4 (int32) or 1 (uint8); H >= h, W >= w (H == h and W == w: no resize);
+ * H, W <= 16384; 1 <= k <= H * W.  Anything else, a NULL pointer or a workspace below manet_loss_ce_topk_workspace_bytes
+ * returns MANET_E_INVALID before anything reaches a device.  No allocation, no synchronisation, no float atomics: loss and
+ * gradient are the same bits for the same shape.
+ *   manet_loss_ce_pixels_f32         pixel_losses [B][H*W] = logsumexp_c(v) - v[label], v = the 4 bilinear taps applied per
+ *                                    channel; the [B][C][H][W] upsampled logits are never written.  The source index is the
+ *                                    exact dst * (in - 1) / (out - 1) (integer quotient and remainder), not aten's fp32
+ *                                    scale * dst: within 16 ulp (at the largest |logit|) of the float64 composition.
+ *   manet_loss_ce_topk_forward_f32   the pixel pass (pixel_losses is kept: the backward's input), an exact radix select of
+ *                                    each row's k-th largest loss (no sort) -> t [B], n_gt [B] = #{loss > t}, n_eq [B] =
+ *                                    #{loss == t}, and *loss_out = sum_b (sum_{loss > t} loss + (k - n_gt) t) / divisor,
+ *                                    summed in double in a fixed order.  divisor: B * k for the reference's mean over [B][k];
+ *                                    with k = H * W and divisor = the number of pixels whose label is not 255 this is
+ *                                    CrossEntropyLoss(reduction='mean').
+ *   manet_loss_ce_topk_backward_f32  grad_logits [B][C][h][w] contiguous = sum over pixels of weight * (softmax - onehot) *
+ *                                    grad_out[0] / divisor through the transposed taps (a gather per low-resolution
+ *                                    position, fixed order).  grad_out: ONE float in device memory.
+ * Deviations from the reference, all outside its contract (ties and NaN: the notes at the top of this file):
+ *   labels    255 is ignore_index: loss 0, no gradient.  Any other label outside 0..C-1 (the reference faults on it) is
+ *             treated the same way.
+ *   ties      weight 1 above t, (k - n_gt) / n_eq for each of the n_eq pixels at t.  With k or more NaN pixels t itself is
+ *             NaN and the NaN pixels share the weight like any tie. */
+int manet_loss_ce_topk_workspace_bytes(int B, int H, int W, size_t *bytes);
+int manet_loss_ce_pixels_f32(const float *logits, int64_t l_sb, int64_t l_sc, int64_t l_sy, int64_t l_sx, const void *labels,
+                             int label_elem_size, int64_t y_sb, int64_t y_sy, int64_t y_sx, int B, int C, int h, int w, int H,
+                             int W, float *pixel_losses, manet_stream_t stream);
+int manet_loss_ce_topk_forward_f32(const float *logits, int64_t l_sb, int64_t l_sc, int64_t l_sy, int64_t l_sx,
+                                   const void *labels, int label_elem_size, int64_t y_sb, int64_t y_sy, int64_t y_sx, int B,
+                                   int C, int h, int w, int H, int W, int64_t k, float divisor, float *pixel_losses,
+                                   float *loss_out, float *t_out, int32_t *n_gt_out, int32_t *n_eq_out, void *ws,
+                                   size_t ws_bytes, manet_stream_t stream);
+int manet_loss_ce_topk_backward_f32(const float *logits, int64_t l_sb, int64_t l_sc, int64_t l_sy, int64_t l_sx,
+                                    const void *labels, int label_elem_size, int64_t y_sb, int64_t y_sy, int64_t y_sx, int B,
+                                    int C, int h, int w, int H, int W, int64_t k, float divisor, const float *pixel_losses,
+                                    const float *t, const int32_t *n_gt, const int32_t *n_eq, const float *grad_out,
+                                    float *grad_logits, manet_stream_t stream);
 
 /* DynamicSegHead's output layer, fused (networks/IntVOS.py:519,525: Conv2d(embed_dim, 1, kernel 1) on layer4's ReLU
  * output): out[b][p] = bias[0] + sum_c weight[c] * (relu_in ? max(in[b][c][p], 0) : in[b][c][p]).
