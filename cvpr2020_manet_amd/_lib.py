@@ -112,6 +112,15 @@ SIGNATURES = {
     "manet_bn_relu_workspace_bytes": (_i, [_i, _i, _i, _szp]),
     "manet_bn_relu_forward_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "manet_bn_relu_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "manet_out_conv_workspace_bytes": (_i, [_i, _i, _i, _szp]),
+    "manet_bn_relu_outconv_forward_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "manet_bn_relu_outconv_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                                _vp]),
+    "manet_out_conv_forward_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "manet_out_conv_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "manet_head_train_bytes": (_i, [_i, _i, _i, _i, _i, _i, _szp, _szp]),
+    "manet_head_train_forward_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "manet_head_train_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "manet_loss_ce_topk_workspace_bytes": (_i, [_i, _i, _i, _szp]),
     "manet_loss_ce_pixels_f32": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "manet_loss_ce_topk_forward_f32": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i64, _f,

@@ -20,6 +20,11 @@ pointers, so the backward is explicit:
                   (csrc/pw_train.hip); ops.pointwise_conv2d, IntVOS(train_kernels="all").
   BatchNormReluFn  the heads' BatchNorm + ReLU pairs in training (or eval with grad enabled): statistics, running buffers and
                   the backward on csrc/pw_train.hip's kernels; ops.batch_norm_relu, IntVOS(train_kernels="all").
+  OutputConvFn     DynamicSegHead's output conv (IntVOS.py:516,524) in training: forward and a deterministic backward
+                  (csrc/head_train.hip); ops.output_conv1x1.
+  DynamicSegHeadFn  a whole DynamicSegHead's training step as one node: the existing depthwise, BatchNorm + ReLU and 1x1
+                  launchers sequenced in C, the output conv fused with the BatchNorm + ReLU in front of it
+                  (csrc/head_train.hip); ops.dynamic_seghead_train, IntVOS(train_kernels="fused").
   UpsampledCrossEntropyTopKFn  the loss behind the head (train_stage1.py:126-153, networks/loss.py:44-81): bilinear upsample,
                   cross-entropy, hard-pixel top-k and mean as one op, deterministic forward and backward (csrc/loss_train.hip);
                   ops.upsampled_cross_entropy_topk, networks.loss.Added_CrossEntropyLoss.
@@ -455,6 +460,120 @@ class BatchNormReluFn(torch.autograd.Function):
                                                       None if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(dev)),
                        "manet_bn_relu_backward_f32")
         return gx, gw, gb, None, None, None, None, None
+
+
+class OutputConvFn(torch.autograd.Function):
+    """DynamicSegHead's output layer in training (IntVOS.py:516,524): F.conv2d(x, weight, bias) with a [1, C, 1, 1] weight, fp32
+    NCHW.  Forward manet_out_conv_forward_f32; backward manet_out_conv_backward_f32 (grad_x = weight[c] * g; grad_weight and
+    grad_bias through per-tile partials added in a fixed order: deterministic), asked only for the gradients needed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from . import ops
+        x = x.contiguous()
+        wt = weight.detach().contiguous()
+        with torch.no_grad():
+            out = ops._out_conv_forward(x, wt, bias)
+        ctx.save_for_backward(x, wt)
+        ctx.has_bias = bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import ops
+        x, wt = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
+        if not (need_x or need_w or need_b):
+            return None, None, None
+        B, C, h, w = x.shape
+        dev = x.device
+        g = grad_out.contiguous().float()
+        gx = torch.empty_like(x) if need_x else None
+        gw = torch.empty_like(wt) if need_w else None
+        gb = torch.empty((1,), dtype=torch.float32, device=dev) if need_b else None
+        with ops._on(dev):
+            nbytes = ops._ws_bytes("manet_out_conv_workspace_bytes", B, C, h * w)
+            ws = ops._workspace(dev, "out_conv", nbytes)
+            rc = _lib.load().manet_out_conv_backward_f32(g.data_ptr(), x.data_ptr(), B, C, h * w, wt.data_ptr(),
+                                                         None if gx is None else gx.data_ptr(), None if gw is None else gw.data_ptr(),
+                                                         None if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(dev))
+        _lib.check(rc, "manet_out_conv_backward_f32")
+        return gx, gw, gb
+
+
+def _head_bytes(B, Cin, Cmid, h, w, K):
+    saved, ws = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(_lib.load().manet_head_train_bytes(B, Cin, Cmid, h, w, K, ctypes.byref(saved), ctypes.byref(ws)), "manet_head_train_bytes")
+    return saved.value, ws.value
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+class DynamicSegHeadFn(torch.autograd.Function):
+    """A whole DynamicSegHead (IntVOS.py:509-525: four _split_separable_conv2d blocks and conv = Conv2d(C, 1, 1)) in training as
+    one node: apply(head, x, *params), params = the head's 34 parameters in the order of ops.dynamic_seghead_tensors without the
+    running statistics (a missing bias: None).  Forward manet_head_train_forward_f32 -- the existing depthwise, BatchNorm + ReLU
+    and 1x1 launchers sequenced in C, the output conv fused with layer 4's last BatchNorm + ReLU, running statistics updated in
+    place; the activations the backward reads live in ONE tensor the context keeps.  Backward manet_head_train_backward_f32,
+    told which of the 35 gradients are needed: a frozen input (train_stage2.py:57: the embedding under no_grad) skips layer 1's
+    depthwise backward-data, a frozen parameter its reduction."""
+
+    @staticmethod
+    def forward(ctx, head, x, *params):
+        from . import ops
+        x = x.contiguous()
+        tensors = ops.dynamic_seghead_tensors(head)
+        bns = ops.dynamic_seghead_bns(head)
+        B, Cin, h, w = x.shape
+        Cmid, K = head.conv.in_channels, head.layer1.conv1.kernel_size[0]
+        dev = x.device
+        saved_bytes, ws_bytes = _head_bytes(B, Cin, Cmid, h, w, K)
+        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+        logits = torch.empty((B, 1, h, w), dtype=torch.float32, device=dev)
+        training = (ctypes.c_int * 8)(*[1 if bn.training else 0 for bn in bns])
+        momentum = (ctypes.c_float * 8)(*[float(bn.momentum) for bn in bns])
+        eps = (ctypes.c_float * 8)(*[float(bn.eps) for bn in bns])
+        with ops._on(dev):
+            ws = ops._workspace(dev, "head_train", ws_bytes)
+            rc = _lib.load().manet_head_train_forward_f32(x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(tensors), training, momentum, eps,
+                                                          saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, logits.data_ptr(),
+                                                          _stream_ptr(dev))
+        _lib.check(rc, "manet_head_train_forward_f32")
+        # the backward reads parameters, not running statistics: those slots stay NULL there
+        ctx.slots = [i for i, name in enumerate(ops.HEAD_BLOCK_TENSORS * 4 + ("conv.weight", "conv.bias")) if "running" not in name]
+        ctx.present = [p is not None for p in params]
+        ctx.save_for_backward(x, saved, *[p for p in params if p is not None])
+        ctx.dims = (B, Cin, Cmid, h, w, K)
+        ctx.training = training
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import ops
+        x, saved, *kept = ctx.saved_tensors
+        B, Cin, Cmid, h, w, K = ctx.dims
+        dev = x.device
+        it = iter(kept)
+        params = [next(it) if present else None for present in ctx.present]
+        need = [present and ctx.needs_input_grad[2 + j] for j, present in enumerate(ctx.present)]
+        if not (ctx.needs_input_grad[1] or any(need)):
+            return (None,) * (2 + len(params))
+        g = grad_out.contiguous().float()
+        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        grads = [torch.empty_like(p) if n else None for p, n in zip(params, need)]
+        p50, g50 = [None] * 50, [None] * 50
+        for slot, p, gp in zip(ctx.slots, params, grads):
+            p50[slot], g50[slot] = p, gp
+        saved_bytes, ws_bytes = _head_bytes(B, Cin, Cmid, h, w, K)
+        with ops._on(dev):
+            ws = ops._workspace(dev, "head_train", ws_bytes)
+            rc = _lib.load().manet_head_train_backward_f32(g.data_ptr(), x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(p50), ctx.training,
+                                                           saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, _ptr_array(g50),
+                                                           None if gx is None else gx.data_ptr(), _stream_ptr(dev))
+        _lib.check(rc, "manet_head_train_backward_f32")
+        return (None, gx) + tuple(grads)
 
 
 class UpsampledCrossEntropyTopKFn(torch.autograd.Function):

@@ -67,9 +67,11 @@ def _pointwise_mode(block=None):
 
 
 def _train_mode(on):
-    """the switch's value: "all" (depthwise, BatchNorm + ReLU and the 1x1 convolutions), else bool(on) (True: the depthwise
-    layers)"""
-    return "all" if isinstance(on, str) and on.lower() == "all" else bool(on)
+    """the switch's value: "all" (depthwise, BatchNorm + ReLU and the 1x1 convolutions), "fused" ("all", and a whole
+    DynamicSegHead as one op), else bool(on) (True: the depthwise layers)"""
+    if isinstance(on, str) and on.lower() in ("all", "fused"):
+        return on.lower()
+    return bool(on)
 
 
 def use_train_kernels(module, on=True):
@@ -79,10 +81,14 @@ def use_train_kernels(module, on=True):
     backward -- whenever it is outside the inference fast path (training mode or grad enabled) on fp32 GPU input; BN, the 1x1
     convolutions and the ReLUs stay the framework's modules.  With on = "all" the BatchNorm + ReLU pairs run on
     ops.batch_norm_relu and the 1x1 convolutions on ops.pointwise_conv2d as well (a BatchNorm without affine parameters,
-    running statistics or a numeric momentum keeps the stock modules).  A plain attribute: not a buffer, not in the state dict."""
+    running statistics or a numeric momentum keeps the stock modules).  With on = "fused" everything is as under "all", and a
+    DynamicSegHead whose every layer is eligible runs as ONE autograd node, ops.dynamic_seghead_train: the four blocks and the
+    output conv sequenced in C, the output conv fused with layer 4's last BatchNorm + ReLU, deterministic end to end, no
+    gradient computed for an input or parameter that does not require one.  A head with an ineligible layer goes block by
+    block as under "all", its output conv on ops.output_conv1x1.  A plain attribute: not a buffer, not in the state dict."""
     mode = _train_mode(on)
     for m in module.modules():
-        if isinstance(m, _split_separable_conv2d) or m is module:
+        if isinstance(m, (_split_separable_conv2d, DynamicSegHead)) or m is module:
             object.__setattr__(m, "_train_kernels", mode)
     return module
 
@@ -90,33 +96,67 @@ def use_train_kernels(module, on=True):
 def _train_dw_ok(module, conv, x):
     """conv (a depthwise Conv2d, K = 3 or 7, stride 1, padding K // 2) runs on ops.depthwise_conv2d: the switch is on, the call is
     outside the inference fast path (training mode or grad enabled), and input and weight are fp32 on the GPU"""
-    k = conv.kernel_size[0]
     return (getattr(module, "_train_kernels", False) and (module.training or torch.is_grad_enabled())
-            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.weight.is_cuda
-            and conv.weight.dtype == torch.float32 and conv.kernel_size == (k, k) and k in (3, 7)
+            and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and _dw_ok(conv, x.shape[1]))
+
+
+def _dw_ok(conv, C):
+    """conv is a C-channel depthwise Conv2d ops.depthwise_conv2d computes, with fp32 GPU weights"""
+    k = conv.kernel_size[0]
+    return (conv.weight.is_cuda and conv.weight.dtype == torch.float32 and conv.kernel_size == (k, k) and k in (3, 7)
             and conv.stride == (1, 1) and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1)
-            and conv.groups == conv.in_channels == conv.out_channels == x.shape[1] and conv.padding_mode == "zeros")
+            and conv.groups == conv.in_channels == conv.out_channels == C and conv.padding_mode == "zeros")
+
 
 def _train_all(module, x):
-    """the "all" route applies: switch "all", outside the inference fast path, fp32 GPU input"""
-    return (getattr(module, "_train_kernels", False) == "all" and (module.training or torch.is_grad_enabled())
+    """the "all" route applies: switch "all" (or "fused", which implies it), outside the inference fast path, fp32 GPU input"""
+    return (getattr(module, "_train_kernels", False) in ("all", "fused") and (module.training or torch.is_grad_enabled())
             and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4)
+
+
+def _bn_ok(bn):
+    """bn is a BatchNorm ops.batch_norm_relu takes, with fp32 GPU parameters and running statistics"""
+    return ops.batch_norm_relu_ok(bn) and all(t.is_cuda and t.dtype == torch.float32 for t in (bn.weight, bn.bias, bn.running_mean,
+                                                                                               bn.running_var))
 
 
 def _train_bn_relu(bn, x):
     """relu(bn(x)) of the "all" route: ops.batch_norm_relu, or the stock modules for a BatchNorm it does not take"""
-    if ops.batch_norm_relu_ok(bn) and all(t.is_cuda and t.dtype == torch.float32 for t in (bn.weight, bn.bias, bn.running_mean,
-                                                                                          bn.running_var)):
+    if _bn_ok(bn):
         return ops.batch_norm_relu(x, bn)
     return F.relu(bn(x))
 
 
+def _pw_ok(conv):
+    """conv is a plain 1x1 convolution with fp32 GPU weights"""
+    return (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.weight.is_cuda and conv.weight.dtype == torch.float32)
+
+
 def _train_pw(conv, x):
     """conv(x) of the "all" route: ops.pointwise_conv2d for a plain 1x1 convolution with fp32 GPU weights, else the module"""
-    if (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1)
-            and conv.groups == 1 and conv.weight.is_cuda and conv.weight.dtype == torch.float32):
+    if _pw_ok(conv):
         return ops.pointwise_conv2d(x, conv.weight, conv.bias)
     return conv(x)
+
+
+def _train_fused_ok(head, x):
+    """the whole DynamicSegHead runs as one op (ops.dynamic_seghead_train): switch "fused", outside the inference fast path, fp32
+    GPU input, and EVERY layer eligible -- each block's depthwise conv (_dw_ok; one filter size for the four), BatchNorms
+    (_bn_ok) and 1x1 conv (_pw_ok) as the "all" route asks layer by layer, the block widths chaining, and the output layer a
+    plain Conv2d(C, 1, 1) with fp32 GPU weights"""
+    if not (getattr(head, "_train_kernels", False) == "fused" and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+        return False
+    C, cmid, k = x.shape[1], head.conv.in_channels, head.layer1.conv1.kernel_size
+    for blk in (head.layer1, head.layer2, head.layer3, head.layer4):
+        if not (getattr(blk, "_train_kernels", False) == "fused" and (blk.training or torch.is_grad_enabled())
+                and _dw_ok(blk.conv1, C) and blk.conv1.kernel_size == k and _bn_ok(blk.bn1) and blk.bn1.num_features == C
+                and _pw_ok(blk.conv2) and blk.conv2.in_channels == C and blk.conv2.out_channels == cmid and _bn_ok(blk.bn2)
+                and blk.bn2.num_features == cmid):
+            return False
+        C = cmid
+    return _pw_ok(head.conv) and head.conv.out_channels == 1 and all(
+        t is None or (t.device == x.device and t.is_contiguous()) for t in ops.dynamic_seghead_tensors(head))
 
 
 # arithmetic of the QK^T contraction used by the MODULE-LEVEL functions: "f32" (exact fp32 MFMA) | "bf16" | "bf16x3" |
@@ -443,7 +483,7 @@ def _layer1_fused(layer, shared, global_map, local_map, labels, n_ids, size, mem
 class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
     def __init__(self, in_dim=None, embed_dim=None, kernel_size=1, train_kernels=False):
         """train_kernels: the training route on HIP kernels (use_train_kernels): True the depthwise layers, "all" every
-        layer of the blocks"""
+        layer of the blocks, "fused" the whole head -- blocks and output conv -- as one deterministic op"""
         super().__init__()
         in_dim = cfg.MODEL_SEMANTIC_EMBEDDING_DIM + 3 if in_dim is None else in_dim
         embed_dim = cfg.MODEL_HEAD_EMBEDDING_DIM if embed_dim is None else embed_dim
@@ -473,7 +513,14 @@ class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
     def forward(self, x):
         if self.layer1._fast(x):
             return self._tail(self.layer1(x))
-        return self.conv(self.layer4(self.layer3(self.layer2(self.layer1(x)))))
+        if (self.training or torch.is_grad_enabled()) and _train_fused_ok(self, x):
+            return ops.dynamic_seghead_train(self, x)  # training route "fused" (use_train_kernels): one autograd node
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        if (getattr(self, "_train_kernels", False) == "fused" and _train_all(self, x) and _pw_ok(self.conv)
+                and self.conv.out_channels == 1):
+            # "fused" with an ineligible layer: block by block as under "all", the output conv on its own HIP kernels
+            return ops.output_conv1x1(x, self.conv.weight, self.conv.bias)
+        return self.conv(x)
 
     def forward_shared(self, shared, per_object, memo=None):
         """forward(cat([shared.repeat(n,1,1,1), per_object], 1)) without materialising the input; memo: see
@@ -542,7 +589,8 @@ class IntVOS(nn.Module):
                         torch noticing (HIP-graph replay of the encoder into a static buffer, `.data` writes)
           train_kernels the depthwise layers of the heads (DynamicSegHead's four blocks, the embedding head's 3x3) on HIP forward /
                         backward kernels in training mode or with grad enabled (use_train_kernels); "all": their BatchNorm +
-                        ReLU pairs and 1x1 convolutions too; default off (cfg's MODEL_TRAIN_KERNELS when it has it): the
+                        ReLU pairs and 1x1 convolutions too; "fused": "all", and each DynamicSegHead -- four blocks and the
+                        output conv -- as one deterministic autograd node (ops.dynamic_seghead_train); default off (cfg's MODEL_TRAIN_KERNELS when it has it): the
                         framework's modules, as the reference"""
         super().__init__()
         set_cfg(cfg)

@@ -1169,6 +1169,85 @@ def relu_conv1x1_c1(x, weight, bias=None, relu_in=True):
     return out
 
 
+def _out_conv_check(x, weight, bias):
+    _need_gpu(x, "x")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("x must be a float32 [B, C, h, w] tensor")
+    C = x.shape[1]
+    if weight.dim() != 4 or tuple(weight.shape) != (1, C, 1, 1) or weight.dtype != torch.float32:
+        raise ValueError("weight must be a float32 [1, C, 1, 1] tensor (got %s for C = %d)" % (tuple(weight.shape), C))
+    if bias is not None and (bias.numel() != 1 or bias.dtype != torch.float32):
+        raise ValueError("bias must be a float32 [1] tensor")
+
+
+def _out_conv_forward(x, weight, bias):
+    """bias + sum_c weight[c] x[:, c] on the HIP kernel (manet_out_conv_forward_f32); x, weight contiguous, no autograd"""
+    B, C, h, w = x.shape
+    bz = None if bias is None else bias.detach().contiguous()
+    out = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        rc = _lib.load().manet_out_conv_forward_f32(x.data_ptr(), B, C, h * w, weight.detach().data_ptr(),
+                                                    None if bz is None else bz.data_ptr(), out.data_ptr(), _stream_ptr(x.device))
+    _lib.check(rc, "manet_out_conv_forward_f32")
+    return out
+
+
+def output_conv1x1(x, weight, bias=None):
+    """F.conv2d(x, weight, bias) for a [1, C, 1, 1] weight on HIP kernels, differentiable and deterministic: DynamicSegHead's
+    output layer (IntVOS.py:516,524) in training.  x [B, C, h, w] fp32 on the GPU, bias [1] or None.  With grad wanted the op is
+    autograd.OutputConvFn (forward kernel; one fixed-order reduction and one apply kernel backward), otherwise the forward kernel
+    alone."""
+    _out_conv_check(x, weight, bias)
+    if _wants_grad(x, weight, bias):
+        from .autograd import OutputConvFn
+        return OutputConvFn.apply(x, weight, bias)
+    return _out_conv_forward(x.contiguous(), weight.contiguous(), bias)
+
+
+HEAD_BLOCK_TENSORS = ("conv1.weight", "conv1.bias", "bn1.weight", "bn1.bias", "bn1.running_mean", "bn1.running_var",
+                      "conv2.weight", "conv2.bias", "bn2.weight", "bn2.bias", "bn2.running_mean", "bn2.running_var")
+
+
+def dynamic_seghead_tensors(head):
+    """the head's parameters and running statistics in the order of the C ABI's `params` (MANET_HEAD_PARAMS = 50 entries: twelve
+    per block, HEAD_BLOCK_TENSORS, then conv.weight, conv.bias); a missing bias is None"""
+    out = []
+    for blk in (head.layer1, head.layer2, head.layer3, head.layer4):
+        for name in HEAD_BLOCK_TENSORS:
+            mod, attr = name.split(".")
+            out.append(getattr(getattr(blk, mod), attr))
+    return out + [head.conv.weight, head.conv.bias]
+
+
+def dynamic_seghead_bns(head):
+    """the head's eight BatchNorms in forward order"""
+    return [bn for blk in (head.layer1, head.layer2, head.layer3, head.layer4) for bn in (blk.bn1, blk.bn2)]
+
+
+def dynamic_seghead_train(head, x):
+    """head(x) for a DynamicSegHead (IntVOS.py:509-525) in training, as ONE differentiable op on HIP kernels: the four blocks
+    and the output conv, forward and backward, sequenced in C (manet_head_train_forward_f32 / _backward_f32;
+    autograd.DynamicSegHeadFn), the output conv fused with layer 4's last BatchNorm + ReLU.  x [B, Cin, h, w] fp32 on the GPU.
+    Gradients for x and the head's 34 parameters -- only those that require one; the eight BatchNorms' running_mean /
+    running_var / num_batches_tracked updated as nn.BatchNorm2d does, each BatchNorm's own .training selecting batch or running
+    statistics.  Deterministic: the same bits for the same inputs.  The caller (DynamicSegHead.forward under
+    train_kernels="fused") has checked every layer's eligibility (IntVOS._train_fused_ok)."""
+    _need_gpu(x, "x")
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("x must be a float32 [B, C, h, w] tensor")
+    bns = dynamic_seghead_bns(head)
+    if any(bn.training for bn in bns) and x.shape[0] * x.shape[2] * x.shape[3] == 1:  # (F.batch_norm -> _verify_batch_size)
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(x.size()))
+    from .autograd import DynamicSegHeadFn
+    tensors = dynamic_seghead_tensors(head)
+    params = [t for t, name in zip(tensors, HEAD_BLOCK_TENSORS * 4 + ("conv.weight", "conv.bias")) if "running" not in name]
+    out = DynamicSegHeadFn.apply(head, x, *params)
+    counters = [bn.num_batches_tracked for bn in bns if bn.training and bn.num_batches_tracked is not None]
+    if counters:
+        torch._foreach_add_(counters, 1)  # (one launch for the eight, not eight)
+    return out
+
+
 _LOSS_LABEL_DTYPES = (torch.int64, torch.int32, torch.uint8)
 LOSS_MAX_CHANNELS = 64  # MANET_MAX_IDS
 

@@ -431,6 +431,64 @@ int manet_bn_relu_backward_f32(const float *grad_out, const float *in, int B, in
                                const float *save_mean, const float *save_invstd, int training, float *grad_in, float *grad_gamma,
                                float *grad_beta, void *ws, size_t ws_bytes, manet_stream_t stream);
 
+/* DynamicSegHead's output layer for training, and a whole head's training step behind one call (csrc/head_train.hip):
+ * networks/IntVOS.py:443-476, reference IntVOS.py:509-525 (layer1..layer4 = _split_separable_conv2d, conv = Conv2d(Cmid, 1, 1))
+ * as it runs in train_stage1.py:126-156 and train_stage2.py:57,131-149 (where the optimiser owns this head alone).
+ * fp32, contiguous.  Invalid arguments (non-positive sizes, K other than 3 or 7, NULL pointers, a buffer that is too small or
+ * not 16-byte aligned, one value per channel in training, eps <= 0, momentum outside [0, 1]) return MANET_E_INVALID before
+ * anything is launched.  No allocation, no synchronisation, no float atomics: every reduction writes per-(channel, tile)
+ * partials to the workspace and a second launch adds them in a fixed order, so the bits depend on the shape alone.
+ *
+ * Output layer (IntVOS.py:516,524), weight [C], bias [1] or NULL, logits / grad_logits [B][HW]:
+ *   manet_bn_relu_outconv_forward_f32   z [B][C][HW] = layer 4's conv2 output.  Statistics as manet_bn_relu_forward_f32
+ *       (training != 0: batch statistics, running buffers updated; else the running ones; save_mean / save_invstd [C] receive
+ *       them), then logits[b][p] = bias + sum_c weight[c] * max(bn(z)[b][c][p], 0).  The activation is never written.
+ *   manet_bn_relu_outconv_backward_f32  a = max(bn(z), 0) recomputed, g' = weight[c] * grad_logits * [a > 0]:
+ *       grad_weight[c] = sum g a, grad_bias[0] = sum g, grad_beta = sum g', grad_gamma = sum g' xhat, grad_z = gamma invstd
+ *       (g' - grad_beta / n - xhat grad_gamma / n) (training) or gamma invstd g' (eval).  Any output may be NULL and is
+ *       then not computed.
+ *   manet_out_conv_forward_f32          out[b][p] = bias + sum_c weight[c] * in[b][c][p] (F.conv2d with a [1, C, 1, 1] weight).
+ *   manet_out_conv_backward_f32         grad_in = weight[c] * grad_out, grad_weight[c] = sum_{b,p} grad_out * in, grad_bias[0] =
+ *       sum grad_out; any of the three may be NULL (`in` too when neither grad_weight nor grad_bias is asked for).
+ *   manet_out_conv_workspace_bytes covers all four (the forward needs it in training, or when few pixels make it split the
+ *   channels over workgroups; the backward whenever a reduction is asked for).
+ *
+ * The head.  x [B][Cin][h][w], logits [B][h*w]; the four blocks have Cin, Cmid, Cmid, Cmid input and Cmid output channels and
+ * K x K depthwise filters.  `params` is a HOST array of MANET_HEAD_PARAMS device pointers: per block, in order,
+ *     conv1.weight [C][K][K], conv1.bias [C], bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var [C],
+ *     conv2.weight [Cmid][C], conv2.bias [Cmid], bn2.weight, bn2.bias, bn2.running_mean, bn2.running_var [Cmid]
+ * then conv.weight [Cmid], conv.bias [1].  The convolutions' biases may be NULL.  training / momentum / eps: host arrays of
+ * 8, one entry per BatchNorm in forward order (bn1, bn2 of layer 1, ...); each BatchNorm's own flag selects batch or running
+ * statistics.  `grads` has the order of `params`: a NULL entry is a gradient not wanted (the running statistics' entries are
+ * ignored), and so is a NULL grad_x; nothing is computed that only an unwanted gradient needs.
+ *   manet_head_train_bytes         saved_bytes (activations and statistics the backward reads: per block the depthwise output,
+ *       bn1's output, conv2's output, and -- but for layer 4 -- the block's output) and ws_bytes (the launchers' workspaces and
+ *       two gradient buffers).  saved_bytes <= 4 B h w (3 (Cin + 3 Cmid) + 4 Cmid) + 64 KiB.
+ *   manet_head_train_forward_f32   the existing launchers (manet_dwconv_forward_f32, manet_bn_relu_forward_f32,
+ *       manet_pw_forward_f32) block by block, then manet_bn_relu_outconv_forward_f32; fills `saved`, updates running statistics.
+ *   manet_head_train_backward_f32  the reverse, from the same x, params, training and `saved`. */
+#define MANET_HEAD_PARAMS 50
+int manet_out_conv_workspace_bytes(int B, int C, int HW, size_t *bytes);
+int manet_bn_relu_outconv_forward_f32(const float *z, int B, int C, int HW, const float *gamma, const float *beta,
+                                      float *running_mean, float *running_var, float momentum, float eps, int training,
+                                      const float *weight, const float *bias, float *logits, float *save_mean, float *save_invstd,
+                                      void *ws, size_t ws_bytes, manet_stream_t stream);
+int manet_bn_relu_outconv_backward_f32(const float *grad_logits, const float *z, int B, int C, int HW, const float *gamma,
+                                       const float *beta, const float *save_mean, const float *save_invstd, int training,
+                                       const float *weight, float *grad_z, float *grad_weight, float *grad_bias, float *grad_gamma,
+                                       float *grad_beta, void *ws, size_t ws_bytes, manet_stream_t stream);
+int manet_out_conv_forward_f32(const float *in, int B, int C, int HW, const float *weight, const float *bias, float *out,
+                               manet_stream_t stream);
+int manet_out_conv_backward_f32(const float *grad_out, const float *in, int B, int C, int HW, const float *weight, float *grad_in,
+                                float *grad_weight, float *grad_bias, void *ws, size_t ws_bytes, manet_stream_t stream);
+int manet_head_train_bytes(int B, int Cin, int Cmid, int h, int w, int K, size_t *saved_bytes, size_t *ws_bytes);
+int manet_head_train_forward_f32(const float *x, int B, int Cin, int Cmid, int h, int w, int K, float *const *params,
+                                 const int *training, const float *momentum, const float *eps, void *saved, size_t saved_bytes,
+                                 void *ws, size_t ws_bytes, float *logits, manet_stream_t stream);
+int manet_head_train_backward_f32(const float *grad_logits, const float *x, int B, int Cin, int Cmid, int h, int w, int K,
+                                  float *const *params, const int *training, const void *saved, size_t saved_bytes, void *ws,
+                                  size_t ws_bytes, float *const *grads, float *grad_x, manet_stream_t stream);
+
 /* The training loss behind the head, fused (csrc/loss_train.hip): train_stage1.py:126-153 + networks/loss.py:44-81, i.e.
  *   F.interpolate(logits, (H, W), 'bilinear', align_corners=True) -> CrossEntropyLoss(ignore_index=255, reduction='none')
  *   -> torch.topk(pixel_losses, k, dim=1) -> mean, and its backward.

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """The rest of a head block in training: the framework's 1x1 convolution (F.conv2d + autograd) and BatchNorm + ReLU
 (nn.BatchNorm2d in train() mode + ReLU + autograd) against the HIP kernels of csrc/pw_train.hip, per pass, and one whole
-DynamicSegHead forward + backward in train() mode for train_kernels False, True and "all".  HIP events, warm-up, median of
-repeats.  The 1x1 passes are reported as fractions of the fp32 matrix peak (157.3 TFLOP/s), the BN passes as GB/s of their
-compulsory HBM traffic (forward: read x twice -- statistics, apply -- write out; backward: read x and dy twice, write dx).
-usage: python tools/head_train_bench.py [--reps N] [--json FILE] [--step-only MODE --shape B,C,h,w]"""
+DynamicSegHead forward + backward in train() mode for train_kernels False, True, "all" and "fused".  HIP events, warm-up, median
+of repeats.  The 1x1 passes are reported as fractions of the fp32 matrix peak (157.3 TFLOP/s), the BN passes as GB/s of their
+compulsory HBM traffic (forward: read x twice -- statistics, apply -- write out; backward: read x and dy twice, write dx), and
+beside them the output layer fused with BatchNorm + ReLU (csrc/head_train.hip; forward: read z twice; backward: read z twice,
+write grad_z).
+usage: python tools/head_train_bench.py [--reps N] [--json FILE] [--step-only MODE --shape B,C,h,w [--frozen-input]]"""
 import argparse
 import ctypes
 import json
@@ -111,6 +113,22 @@ def bn_relu(shape, reps):
     for k, passes in (("fwd", 3), ("bwd", 5)):
         r["hip_%s_GBps" % k] = round(passes * act / (r["hip_%s_us" % k] * 1e-6) / 1e9, 1)
         r["fw_%s_GBps" % k] = round(passes * act / (r["fw_%s_us" % k] * 1e-6) / 1e9, 1)
+    # the same BatchNorm + ReLU with the head's output layer behind it
+    wt, b1 = torch.randn(C, device="cuda") / C ** 0.5, torch.randn(1, device="cuda")
+    gl, logits = torch.randn(B, HW, device="cuda"), torch.empty(B, HW, device="cuda")
+    gwt, gb1 = torch.empty_like(wt), torch.empty_like(b1)
+    _lib.check(lib.manet_out_conv_workspace_bytes(B, C, HW, ctypes.byref(n)), "ws")
+    wso = torch.empty(n.value, dtype=torch.uint8, device="cuda")
+    r["outconv_fwd_us"] = timed(lambda: lib.manet_bn_relu_outconv_forward_f32(
+        x.data_ptr(), B, C, HW, bn.weight.data_ptr(), bn.bias.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+        f(bn.momentum), f(bn.eps), 1, wt.data_ptr(), b1.data_ptr(), logits.data_ptr(), save[0].data_ptr(), save[1].data_ptr(),
+        wso.data_ptr(), wso.numel(), st), reps)
+    r["outconv_bwd_us"] = timed(lambda: lib.manet_bn_relu_outconv_backward_f32(
+        gl.data_ptr(), x.data_ptr(), B, C, HW, bn.weight.data_ptr(), bn.bias.data_ptr(), save[0].data_ptr(), save[1].data_ptr(), 1,
+        wt.data_ptr(), gx.data_ptr(), gwt.data_ptr(), gb1.data_ptr(), gg.data_ptr(), gbe.data_ptr(), wso.data_ptr(), wso.numel(),
+        st), reps)
+    for k, passes in (("fwd", 2), ("bwd", 3)):
+        r["outconv_%s_GBps" % k] = round(passes * act / (r["outconv_%s_us" % k] * 1e-6) / 1e9, 1)
     for k in list(r):
         if k.endswith("_us"):
             r[k] = round(r[k], 1)
@@ -123,11 +141,12 @@ def _head(mode, C):
 
 
 def head_step(shape, reps):
-    """DynamicSegHead(in_dim=C) forward + backward in train() mode, for train_kernels False / True / "all" (same parameters)"""
+    """DynamicSegHead(in_dim=C) forward + backward in train() mode, for train_kernels False / True / "all" / "fused" (same
+    parameters)"""
     B, C, h, w = shape
     x = torch.randn(shape, device="cuda", requires_grad=True)
     r = {"shape": list(shape)}
-    for name, mode in (("framework", False), ("hip_dw", True), ("hip_all", "all")):
+    for name, mode in (("framework", False), ("hip_dw", True), ("hip_all", "all"), ("hip_fused", "fused")):
         head = _head(mode, C)
 
         def step():
@@ -135,6 +154,7 @@ def head_step(shape, reps):
             head(x).sum().backward()
         r[name + "_us"] = round(timed(step, reps), 1)
     r["all_vs_dw"] = round(r["hip_dw_us"] / r["hip_all_us"], 2)
+    r["fused_vs_all"] = round(r["hip_all_us"] / r["hip_fused_us"], 2)
     return r
 
 
@@ -142,15 +162,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--step-only", default=None, help="False | True | all: only run that head step (for a profiler)")
+    ap.add_argument("--step-only", default=None, help="False | True | all | fused: only run that head step (for a profiler)")
     ap.add_argument("--shape", default="3,256,104,104")
+    ap.add_argument("--frozen-input", action="store_true", help="--step-only: x does not require grad (the reference's stage 2)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     if a.step_only is not None:
         shape = tuple(int(v) for v in a.shape.split(","))
         mode = {"false": False, "true": True}.get(a.step_only.lower(), a.step_only)
         head = _head(mode, shape[1])
-        x = torch.randn(shape, device="cuda", requires_grad=True)
+        x = torch.randn(shape, device="cuda", requires_grad=not a.frozen_input)
 
         def step():
             head.zero_grad(set_to_none=True)
@@ -173,14 +194,16 @@ def main():
         print("    %-24s | %8.1f %8.1f %8.1f | %8.1f %8.1f %8.1f   (%.2f / %.2f / %.2f)" % (
             str(tuple(r["shape"])), r["fw_fwd_us"], r["fw_bwd_data_us"], r["fw_bwd_weight_us"], r["hip_fwd_us"],
             r["hip_bwd_data_us"], r["hip_bwd_weight_us"], r["hip_fwd_peak"], r["hip_bwd_data_peak"], r["hip_bwd_weight_peak"]))
-    print("BN+ReLU %-20s | %8s %8s | %8s %8s   (us; GB/s of the HIP pass)" % ("[B,C,h,w]", "fw fwd", "fw bwd", "hip fwd", "hip bwd"))
+    print("BN+ReLU %-20s | %8s %8s | %8s %8s   (us; GB/s of the HIP pass) | %8s %8s   (BN + ReLU + output conv: us; GB/s)" % (
+        "[B,C,h,w]", "fw fwd", "fw bwd", "hip fwd", "hip bwd", "oc fwd", "oc bwd"))
     for r in bn:
-        print("        %-20s | %8.1f %8.1f | %8.1f %8.1f   (%.0f / %.0f)" % (
+        print("        %-20s | %8.1f %8.1f | %8.1f %8.1f   (%.0f / %.0f) | %8.1f %8.1f   (%.0f / %.0f)" % (
             str(tuple(r["shape"])), r["fw_fwd_us"], r["fw_bwd_us"], r["hip_fwd_us"], r["hip_bwd_us"], r["hip_fwd_GBps"],
-            r["hip_bwd_GBps"]))
+            r["hip_bwd_GBps"], r["outconv_fwd_us"], r["outconv_bwd_us"], r["outconv_fwd_GBps"], r["outconv_bwd_GBps"]))
     for r in heads:
-        print("DynamicSegHead train step %s: framework %.1f us, HIP depthwise %.1f us, HIP all %.1f us (%.2fx over depthwise)" % (
-            tuple(r["shape"]), r["framework_us"], r["hip_dw_us"], r["hip_all_us"], r["all_vs_dw"]))
+        print("DynamicSegHead train step %s: framework %.1f us, HIP depthwise %.1f us, HIP all %.1f us (%.2fx over depthwise), "
+              "HIP fused %.1f us (%.2fx over all)" % (tuple(r["shape"]), r["framework_us"], r["hip_dw_us"], r["hip_all_us"],
+                                                       r["all_vs_dw"], r["hip_fused_us"], r["fused_vs_all"]))
     res = {"device": torch.cuda.get_device_name(0), "pointwise": pw, "bn_relu": bn, "head_step": heads}
     print(json.dumps(res))
     if a.json:
