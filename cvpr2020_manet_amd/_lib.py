@@ -72,6 +72,15 @@ SIGNATURES = {
     "manet_local_match_backward_workspace_bytes": (_i, [_i, _i, _i, _i, _szp]),
     "manet_local_match_backward_f32": (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _i,
                                             _i, _i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
+    "manet_global_match_backward_ordered_workspace_bytes": (_i, [_i64, _i64, _i, _i, _i, _szp]),
+    "manet_global_match_backward_ordered_f32": (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i, _i, _i, _vp,
+                                                     _i64, _i64, _vp, _i64, _i64, _vp, _sz, _vp]),
+    "manet_local_match_train_forward_f32": (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i, _i, _i, _i, _i, _vp,
+                                                 _vp, _vp, _vp, _sz, _vp]),
+    "manet_local_match_train_workspace_bytes": (_i, [_i, _i, _i, _i, _i, _szp]),
+    "manet_local_match_train_backward_f32": (_i, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i, _i, _i,
+                                                  _i, _i, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
+    "manet_local_match_full_backward_ordered_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "manet_conv1x1_f32": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp, _i, _i, _vp, _vp]),
     "manet_conv1x1_head_f32": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "manet_conv1x1_add_f32": (_i, [_vp, _i64, _i, _i, _i64, _vp, _vp, _vp, _i, _i, _vp, _vp]),

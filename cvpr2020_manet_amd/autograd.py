@@ -29,6 +29,12 @@ pointers, so the backward is explicit:
                   cross-entropy, hard-pixel top-k and mean as one op, deterministic forward and backward (csrc/loss_train.hip);
                   ops.upsampled_cross_entropy_topk, networks.loss.Added_CrossEntropyLoss.
 
+  GlobalMatchOrderedFn, GlobalMatchTopkOrderedFn, LocalMatchOrderedFn, LocalMatchFullOrderedFn  the ordered training route of
+                  the four matching nodes above (csrc/match_train.hip; ops.global_match / ops.local_match(deterministic=True),
+                  IntVOS(train_match="ordered")): the same forward values and selections, a backward without float atomics --
+                  every sum has one owner and a fixed order, so the gradients are the same bits on every run; all k ranks of the
+                  top-k backward in one call; a frozen operand gets None and costs nothing.
+
 `ops.global_match` / `ops.local_match` / `ops.correlation_forward` route here when grad mode is on and an
 embedding requires grad; normalisation and the min-merge with the stored map stay ordinary torch ops on the
 result (they are element-wise and torch differentiates them).  fp32 only; anything else raises.
@@ -179,6 +185,66 @@ class GlobalMatchTopkFn(torch.autograd.Function):
         return gr_sum, gq_sum, None, None, None
 
 
+def _global_backward_ordered(ref, qry, arg, gw, n_ids, ranks, need_ref, need_qry):
+    """manet_global_match_backward_ordered_f32 on arg / gw [ranks, N, n_ids]: gradients in the inputs' own memory order"""
+    from . import ops
+    lib = _lib.load()
+    M0, C = ref.shape
+    N = qry.shape[0]
+    dev = qry.device
+    gq = gr = None
+    if need_qry:
+        gq = torch.empty_strided(qry.shape, qry.stride(), dtype=torch.float32, device=dev) \
+            if _dense(qry) else torch.empty(qry.shape, dtype=torch.float32, device=dev)
+    if need_ref:
+        gr = torch.empty_strided(ref.shape, ref.stride(), dtype=torch.float32, device=dev) \
+            if _dense(ref) else torch.empty(ref.shape, dtype=torch.float32, device=dev)
+    with ops._on(dev):
+        nbytes = ops._ws_bytes("manet_global_match_backward_ordered_workspace_bytes", N, M0, C, n_ids, ranks)
+        ws = ops._workspace(dev, "global_backward_ordered", nbytes)
+        rc = lib.manet_global_match_backward_ordered_f32(qry.data_ptr(), qry.stride(0), qry.stride(1), ref.data_ptr(),
+                                                         ref.stride(0) if M0 > 0 else C, ref.stride(1) if M0 > 0 else 1,
+                                                         arg.data_ptr(), gw.data_ptr(), N, M0, C, n_ids, ranks,
+                                                         None if gq is None else gq.data_ptr(),
+                                                         C if gq is None else gq.stride(0), 1 if gq is None else gq.stride(1),
+                                                         None if gr is None else gr.data_ptr(),
+                                                         C if (gr is None or M0 == 0) else gr.stride(0),
+                                                         1 if (gr is None or M0 == 0) else gr.stride(1), ws.data_ptr(), ws.numel(),
+                                                         _stream_ptr(dev))
+    _lib.check(rc, "manet_global_match_backward_ordered_f32")
+    return gr, gq
+
+
+class GlobalMatchOrderedFn(GlobalMatchFn):
+    """GlobalMatchFn with the ordered backward (manet_global_match_backward_ordered_f32, ranks = 1): no float atomics, each bank
+    row's gradient added by one owner in ascending (query, object) order -- the same bits on every run."""
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_arg):
+        ref, qry, arg = ctx.saved_tensors
+        need_ref, need_qry = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_ref or need_qry):
+            return None, None, None, None
+        g = grad_out.contiguous().float()
+        gr, gq = _global_backward_ordered(ref, qry, arg, g, ctx.n_ids, 1, need_ref, need_qry)
+        return gr, gq, None, None
+
+
+class GlobalMatchTopkOrderedFn(GlobalMatchTopkFn):
+    """GlobalMatchTopkFn with the ordered backward: the k ranks' rows and weighted gradients go to ONE call of
+    manet_global_match_backward_ordered_f32 (the atomic route launches once per rank and sums with torch)."""
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ref, qry, arg, wgt = ctx.saved_tensors
+        need_ref, need_qry = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_ref or need_qry):
+            return None, None, None, None, None
+        gw = (grad_out.float().unsqueeze(0) * wgt).contiguous()
+        gr, gq = _global_backward_ordered(ref, qry, arg.contiguous(), gw, ctx.n_ids, ctx.k, need_ref, need_qry)
+        return gr, gq, None, None, None
+
+
 def _dense(t):
     """non-overlapping and dense (a permuted contiguous tensor): empty_strided can mirror its layout"""
     if t.numel() == 0:
@@ -288,6 +354,96 @@ class LocalMatchFullFn(torch.autograd.Function):
                                                          dv.data_ptr(), _stream_ptr(dev))
         _lib.check(rc, "manet_local_match_full_backward_f32")
         return gp.permute(1, 2, 0), gc.permute(1, 2, 0), None, None, None
+
+
+class LocalMatchOrderedFn(torch.autograd.Function):
+    """LocalMatchFn's ordered route: forward manet_local_match_train_forward_f32 (the same out / arg / volume bits, the masked
+    minimum spread over (2d+1) x 2 threads per pixel), backward manet_local_match_train_backward_f32 -- sparse, no float atomics,
+    every pooled cell's gradient added by one owner in an order fixed by indices; a frozen frame gets None and no work."""
+
+    @staticmethod
+    def forward(ctx, prev, cur, labels, n_ids, max_distance):
+        from . import ops
+        lib = _lib.load()
+        h, w, C = cur.shape
+        dev = cur.device
+        P = 2 * max_distance + 1
+        out = torch.empty((h, w, n_ids), dtype=torch.float32, device=dev)
+        arg = torch.empty((h, w, n_ids), dtype=torch.int32, device=dev)
+        vol = torch.empty((P * P, h // 2, w // 2), dtype=torch.float32, device=dev)
+        with ops._on(dev):
+            nbytes = ops._ws_bytes("manet_local_match_arg_workspace_bytes", h, w, C, max_distance)
+            ws = ops._workspace(dev, "local_train", nbytes)
+            rc = lib.manet_local_match_train_forward_f32(prev.data_ptr(), prev.stride(0), prev.stride(1), prev.stride(2),
+                                                         cur.data_ptr(), cur.stride(0), cur.stride(1), cur.stride(2),
+                                                         labels.data_ptr(), h, w, C, n_ids, max_distance, out.data_ptr(),
+                                                         arg.data_ptr(), vol.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                         _stream_ptr(dev))
+        _lib.check(rc, "manet_local_match_train_forward_f32")
+        ctx.save_for_backward(prev, cur, vol, arg)
+        ctx.n_ids, ctx.max_distance = n_ids, max_distance
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from . import ops
+        lib = _lib.load()
+        prev, cur, vol, arg = ctx.saved_tensors
+        need_prev, need_cur = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_prev or need_cur):
+            return None, None, None, None, None
+        h, w, C = cur.shape
+        dev = cur.device
+        g = grad_out.contiguous().float()
+        gp = gc = None
+        if need_prev:
+            gp = torch.empty_strided(prev.shape, prev.stride(), dtype=torch.float32, device=dev) \
+                if _dense(prev) else torch.empty(prev.shape, dtype=torch.float32, device=dev)
+        if need_cur:
+            gc = torch.empty_strided(cur.shape, cur.stride(), dtype=torch.float32, device=dev) \
+                if _dense(cur) else torch.empty(cur.shape, dtype=torch.float32, device=dev)
+        with ops._on(dev):
+            nbytes = ops._ws_bytes("manet_local_match_train_workspace_bytes", h, w, C, ctx.n_ids, ctx.max_distance)
+            ws = ops._workspace(dev, "local_train_backward", nbytes)
+            rc = lib.manet_local_match_train_backward_f32(prev.data_ptr(), prev.stride(0), prev.stride(1), prev.stride(2),
+                                                          cur.data_ptr(), cur.stride(0), cur.stride(1), cur.stride(2),
+                                                          vol.data_ptr(), arg.data_ptr(), g.data_ptr(), h, w, C, ctx.n_ids,
+                                                          ctx.max_distance, None if gp is None else gp.data_ptr(),
+                                                          *((0, 0, 0) if gp is None else gp.stride()),
+                                                          None if gc is None else gc.data_ptr(),
+                                                          *((0, 0, 0) if gc is None else gc.stride()), ws.data_ptr(), ws.numel(),
+                                                          _stream_ptr(dev))
+        _lib.check(rc, "manet_local_match_train_backward_f32")
+        return gp, gc, None, None, None
+
+
+class LocalMatchFullOrderedFn(LocalMatchFullFn):
+    """LocalMatchFullFn (MODEL_LOCAL_DOWNSAMPLE = False) with the ordered backward: one owner per (offset, pixel) adds the
+    pixel's objects in ascending order (manet_local_match_full_backward_ordered_f32); a frozen frame gets None."""
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        prev, cur, arg = ctx.saved_tensors
+        need_prev, need_cur = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_prev or need_cur):
+            return None, None, None, None, None
+        h, w, C = cur.shape
+        dev = cur.device
+        P = 2 * ctx.max_distance + 1
+        g = grad_out.contiguous().float()
+        pc, cc = prev.permute(2, 0, 1).contiguous(), cur.permute(2, 0, 1).contiguous()  # (no copy for C-major embeddings)
+        gp = torch.empty_like(pc) if need_prev else None
+        gc = torch.empty_like(cc) if need_cur else None
+        dv = torch.empty((P * P, h * w), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.manet_local_match_full_backward_ordered_f32(pc.data_ptr(), cc.data_ptr(), arg.data_ptr(), g.data_ptr(), h, w,
+                                                                 C, ctx.n_ids, ctx.max_distance,
+                                                                 None if gp is None else gp.data_ptr(),
+                                                                 None if gc is None else gc.data_ptr(), dv.data_ptr(),
+                                                                 _stream_ptr(dev))
+        _lib.check(rc, "manet_local_match_full_backward_ordered_f32")
+        return (None if gp is None else gp.permute(1, 2, 0)), (None if gc is None else gc.permute(1, 2, 0)), None, None, None
 
 
 class CorrelationFn(torch.autograd.Function):

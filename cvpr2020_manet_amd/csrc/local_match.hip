@@ -1553,4 +1553,33 @@ int manet_local_match_full_backward_f32(const float *prev_chw, const float *cur_
     return manet_check_launch("manet_local_match_full_backward_f32");
 }
 
+/* The training forward of the ordered route (csrc/match_train.hip): manet_local_match_arg_f32's pooling and distance launches, then
+ * the masked minimum and the winning offset by mt_local_min_arg_kernel.  Same arguments, same workspace, same bits in out /
+ * arg_out / vol_out. */
+int manet_local_match_train_forward_f32(const float *prev, int64_t p_sy, int64_t p_sx, int64_t p_sc, const float *cur,
+                                        int64_t c_sy, int64_t c_sx, int64_t c_sc, const int32_t *prev_labels, int h, int w, int C,
+                                        int n_ids, int max_distance, float *out, int32_t *arg_out, float *vol_out, void *workspace,
+                                        size_t workspace_bytes, manet_stream_t stream)
+{
+    int rc = check_local(h, w, C, max_distance, 1);
+    if (rc) return rc;
+    if (n_ids <= 0 || n_ids > MANET_MAX_IDS)
+        return manet_set_error(MANET_E_INVALID, "n_ids=%d (supported 1..%d)", n_ids, MANET_MAX_IDS);
+    if (!cur || !prev || !prev_labels || !out || !arg_out || !vol_out) return manet_set_error(MANET_E_INVALID, "null pointer");
+    LocalLayout L = local_layout(h, w, C, max_distance, 1);
+    if (!workspace || workspace_bytes < L.total)
+        return manet_set_error(MANET_E_WORKSPACE, "local workspace %zu < %zu bytes", workspace_bytes, L.total);
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    float *ap = (float *)(ws + L.off_ap), *bp = (float *)(ws + L.off_bp);
+    long n = (long)C * L.hp * L.wp;
+    hipLaunchKernelGGL(pool2x2_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cur, (long)c_sy, (long)c_sx,
+                       (long)c_sc, prev, (long)p_sy, (long)p_sx, (long)p_sc, C, L.hp, L.wp, ap, bp);
+    long plane = (long)L.hp * L.wp;
+    launch_dist(max_distance, st, (const float *)ap, (long)L.wp, 1L, plane, (const float *)bp, (long)L.wp, 1L, plane, L.hp,
+                L.wp, C, 1, vol_out);
+    manet_mt_launch_local_min_arg((const float *)vol_out, prev_labels, h, w, L.hp, L.wp, max_distance, n_ids, out, arg_out, st);
+    return manet_check_launch("manet_local_match_train_forward_f32");
+}
+
 }  // extern "C"

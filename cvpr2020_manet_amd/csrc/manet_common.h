@@ -45,6 +45,11 @@ enum { MANET_TUNE_BLOCK_MAP = 0, MANET_TUNE_SPLITS = 1, MANET_TUNE_BF16_VARIANT 
        MANET_TUNE_COUNT = 15 };
 int manet_tune_get(int key, int dflt);
 
+// csrc/match_train.hip: masked minimum + winning window offset of the training forward on a normalised pooled volume
+// [(2d+1)^2][hp][wp] (the tail of manet_local_match_train_forward_f32; local_min_arg_kernel's bits)
+void manet_mt_launch_local_min_arg(const float *vol, const int32_t *labels, int h, int w, int hp, int wp, int d, int n_ids,
+                                   float *out, int32_t *arg, hipStream_t st);
+
 static inline size_t manet_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Per-frame operands written by manet_frame_prepare (csrc/global_match.hip), read by manet_global_match_prepared_ex

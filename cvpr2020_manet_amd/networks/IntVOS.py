@@ -163,6 +163,25 @@ def _train_fused_ok(head, x):
 # "bf16r".  An IntVOS instance carries its own (constructor argument / cfg.MODEL_MATCH_COMPUTE).
 COMPUTE = "f32"
 
+# backward of the matching functions when they are differentiated, for the MODULE-LEVEL functions: "atomic" (float atomicAdd
+# scatter: the gradients' last bits depend on arrival order) | "ordered" (csrc/match_train.hip: one owner per sum, a fixed order,
+# the same bits on every run).  An IntVOS instance carries its own (constructor argument / cfg.MODEL_TRAIN_MATCH).
+TRAIN_MATCH = "atomic"
+_TRAIN_MATCH_MODES = ("atomic", "ordered")
+
+
+def _train_match_mode(value):
+    if value not in _TRAIN_MATCH_MODES:
+        raise ValueError("train_match=%r ('atomic' or 'ordered')" % (value,))
+    return value
+
+
+def _match_route(train_match):
+    """keyword of ops.global_match / ops.local_match for a route (None: the module's TRAIN_MATCH); the default route calls the
+    ops exactly as before"""
+    mode = _train_match_mode(TRAIN_MATCH if train_match is None else train_match)
+    return {"deterministic": True} if mode == "ordered" else {}
+
 
 def set_cfg(new_cfg):
     global cfg
@@ -188,12 +207,13 @@ def _n_ids_from(gt_ids, reference_labels_flat):
 
 
 def nearest_neighbor_features_per_object(reference_embeddings, query_embeddings, reference_labels,
-                                         k_nearest_neighbors, gt_ids=None, n_chunks=100):
+                                         k_nearest_neighbors, gt_ids=None, n_chunks=100, train_match=None):
     """Distance to the nearest reference pixel per object (reference IntVOS.py:160-210).
 
     reference_embeddings [h_r, w_r, C], query_embeddings [h, w, C], reference_labels [h_r, w_r, 1]
     int.  Returns (nn_features float32 [1, h, w, n_ids, 1], ids int32 [n_ids]).
     `n_chunks` is ignored: the fused kernel tiles the bank through LDS instead of chunking queries.
+    train_match (this implementation's only): the backward when differentiated, default the module's TRAIN_MATCH.
     """
     assert reference_embeddings.size()[:2] == reference_labels.size()[:2]  # IntVOS.py:189
     h, w, _ = query_embeddings.size()
@@ -205,7 +225,7 @@ def nearest_neighbor_features_per_object(reference_embeddings, query_embeddings,
         reference_embeddings = reference_embeddings.reshape(-1, reference_embeddings.shape[-1])[keep]
         labels_flat = labels_flat[keep]
     out = ops.global_match(reference_embeddings, query_embeddings, labels_flat, n_ids,
-                           k_nearest_neighbors=k_nearest_neighbors, compute=COMPUTE)
+                           k_nearest_neighbors=k_nearest_neighbors, compute=COMPUTE, **_match_route(train_match))
     ids = torch.arange(0, n_ids, dtype=torch.int32, device=out.device)
     return out.view(1, h, w, n_ids, 1), ids
 
@@ -258,14 +278,15 @@ def local_pairwise_distances(x, y, max_distance=9):
 
 def local_previous_frame_nearest_neighbor_features_per_object(prev_frame_embedding, query_embedding,
                                                               prev_frame_labels, gt_ids,
-                                                              max_distance=12):
+                                                              max_distance=12, train_match=None):
     """Nearest-neighbour distance per object inside a local window of the previous frame
     (reference IntVOS.py:345-434, unfold path).  gt_ids: int tensor [n_ids] = 0..n_ids-1.
-    Returns float32 [1, h, w, n_ids, 1]."""
+    Returns float32 [1, h, w, n_ids, 1].  train_match (this implementation's only): the route when differentiated, default
+    the module's TRAIN_MATCH."""
     h, w = prev_frame_embedding.size()[:2]
     n_ids = int(gt_ids.size(0))
     out = ops.local_match(prev_frame_embedding, query_embedding, prev_frame_labels, n_ids,
-                          max_distance=max_distance, downsample=bool(cfg.MODEL_LOCAL_DOWNSAMPLE))
+                          max_distance=max_distance, downsample=bool(cfg.MODEL_LOCAL_DOWNSAMPLE), **_match_route(train_match))
     return out.view(1, h, w, n_ids, 1)
 
 
@@ -574,7 +595,7 @@ class IntVOS(nn.Module):
     """reference IntVOS.py:530-764: same constructor, methods, dict conventions, state-dict keys."""
 
     def __init__(self, cfg, feature_extracter, compute=None, emb_dtype=None, pointwise=None, cache_frames=None,
-                 train_kernels=None):
+                 train_kernels=None, train_match=None):
         """cfg, feature_extracter: as the reference.  The rest is optional and this implementation's only (default: the
         cfg's MODEL_MATCH_COMPUTE / MODEL_EMB_DTYPE / MODEL_HEAD_POINTWISE / MODEL_CACHE_FRAMES when it has them, else
         "f32" / "f32" / "f32" / True):
@@ -591,7 +612,12 @@ class IntVOS(nn.Module):
                         backward kernels in training mode or with grad enabled (use_train_kernels); "all": their BatchNorm +
                         ReLU pairs and 1x1 convolutions too; "fused": "all", and each DynamicSegHead -- four blocks and the
                         output conv -- as one deterministic autograd node (ops.dynamic_seghead_train); default off (cfg's MODEL_TRAIN_KERNELS when it has it): the
-                        framework's modules, as the reference"""
+                        framework's modules, as the reference
+          train_match   backward of the global and local match in training: "atomic" (default; cfg's MODEL_TRAIN_MATCH when it has
+                        it) the float-atomicAdd scatter -- the gradient that reaches the embedding head and the encoder can differ
+                        in its last bits from run to run; "ordered" the atomic-free kernels of csrc/match_train.hip: the same bits
+                        on every run (with train_kernels="fused" and the fused loss the whole step behind the encoder is
+                        reproducible), a sparse local backward and a faster training forward of the local match"""
         super().__init__()
         set_cfg(cfg)
         self.cfg = cfg
@@ -647,6 +673,8 @@ class IntVOS(nn.Module):
         tk = train_kernels if train_kernels is not None else getattr(cfg, "MODEL_TRAIN_KERNELS", False)
         self.train_kernels = _train_mode(tk)
         use_train_kernels(self, self.train_kernels)
+        # (a plain attribute: not a buffer, not in the state dict)
+        self.train_match = _train_match_mode(train_match if train_match is not None else getattr(cfg, "MODEL_TRAIN_MATCH", "atomic"))
 
     def _prepared_bank(self, seq_name, ref_emb_chw, ref_label, ref_emb_hwc, ref_lab_flat, n_ids):
         """The sorted / packed memory bank of the annotated frame, reused while the caller keeps passing the SAME
@@ -1227,7 +1255,7 @@ class IntVOS(nn.Module):
                 nn_features_n = ops.global_match(ref_emb, seq_current_frame_embedding, ref_lab() if callable(ref_lab) else ref_lab,
                                                  n_ids, k_nearest_neighbors=k_nearest_neighbors, compute=self.compute,
                                                  normalize=bool(normalize_nearest_neighbor_distances),
-                                                 mem=mem).view(1, h, w, n_ids, 1)
+                                                 mem=mem, **_match_route(self.train_match)).view(1, h, w, n_ids, 1)
 
             # ---- local map
             seq_previous_frame_label = scale_previous_frame_label[n].permute(1, 2, 0)
@@ -1248,12 +1276,12 @@ class IntVOS(nn.Module):
                 prev_frame_nn_features_n = local_previous_frame_nearest_neighbor_features_per_object(
                     prev_frame_embedding=seq_prev_frame_embedding, query_embedding=seq_current_frame_embedding,
                     prev_frame_labels=seq_previous_frame_label, gt_ids=ref_obj_ids,
-                    max_distance=cfg.MODEL_MAX_LOCAL_DISTANCE)
+                    max_distance=cfg.MODEL_MAX_LOCAL_DISTANCE, train_match=self.train_match)
             else:
                 prev_frame_nn_features_n = ops.global_match(
                     seq_prev_frame_embedding, seq_current_frame_embedding, seq_previous_frame_label.reshape(-1),
                     n_ids, k_nearest_neighbors=k_nearest_neighbors, compute=self.compute,
-                    normalize=True).view(1, h, w, n_ids, 1)
+                    normalize=True, **_match_route(self.train_match)).view(1, h, w, n_ids, 1)
 
             # ---- local map memory (:638-661)
             if local_map_dics is not None:
@@ -1362,7 +1390,8 @@ class IntVOS(nn.Module):
             else:
                 nn_features_n = local_previous_frame_nearest_neighbor_features_per_object(
                     prev_frame_embedding=seq_ref_frame_embedding, query_embedding=seq_ref_frame_embedding,
-                    prev_frame_labels=seq_ref_scribble_label, gt_ids=gt_id, max_distance=cfg.MODEL_MAX_LOCAL_DISTANCE)
+                    prev_frame_labels=seq_ref_scribble_label, gt_ids=gt_id, max_distance=cfg.MODEL_MAX_LOCAL_DISTANCE,
+                    train_match=self.train_match)
             # ---- global map update (:716-723): min-merge of THIS map into the stored one
             if seq_names[n] not in global_map_tmp_dic:
                 global_map_tmp_dic[seq_names[n]] = torch.ones_like(nn_features_n).repeat(MAX_CLIP_FRAMES, 1, 1, 1, 1)

@@ -50,11 +50,13 @@ def _wants_grad(*tensors):
 
 
 def _global_match_autograd(reference_embeddings, query_embeddings, reference_labels, n_ids, k_nearest_neighbors,
-                           compute, normalize, mem):
+                           compute, normalize, mem, deterministic=False):
     """Training route of global_match (train_stage1.py:126-156 back-propagates through it): the arg-min forward +
     explicit backward of autograd.GlobalMatchFn; normalisation (IntVOS.py:611-612) and the min-merge with the
     stored map (:620-622, the stored copy detached as in the reference) are ordinary differentiable torch ops."""
-    from .autograd import GlobalMatchFn, GlobalMatchTopkFn
+    from .autograd import GlobalMatchFn, GlobalMatchTopkFn, GlobalMatchOrderedFn, GlobalMatchTopkOrderedFn
+    if deterministic:  # the ordered backward (csrc/match_train.hip): no float atomics, the same gradient bits on every run
+        GlobalMatchFn, GlobalMatchTopkFn = GlobalMatchOrderedFn, GlobalMatchTopkOrderedFn
     if COMPUTE[compute] != _lib.COMPUTE_F32 or not 1 <= k_nearest_neighbors <= 8:
         raise RuntimeError("cvpr2020_manet_amd.ops.global_match: the backward exists for compute='f32' and "
                            "k_nearest_neighbors 1..8 only (got k=%d, compute=%r)" % (k_nearest_neighbors, compute))
@@ -149,16 +151,18 @@ def _labels(t, name):
 
 
 def global_match(reference_embeddings, query_embeddings, reference_labels, n_ids, k_nearest_neighbors=1,
-                 compute="f32", normalize=False, mem=None):
+                 compute="f32", normalize=False, mem=None, deterministic=False):
     """nearest_neighbor_features_per_object on the HIP path (IntVOS.py:160-210), optionally with the
     fused normalise (IntVOS.py:611-612) and min-merge into `mem` (IntVOS.py:620-622, in place).
 
     Returns float32 [N, n_ids] (N = number of query pixels), raw or normalised distances.
+    deterministic=True: when the call is differentiated, the backward is the ordered, atomic-free one (the same gradient bits
+    on every run); forward values are the same either way.
     """
     import ctypes
     if _wants_grad(reference_embeddings, query_embeddings, mem):
         return _global_match_autograd(reference_embeddings, query_embeddings, reference_labels, n_ids,
-                                      k_nearest_neighbors, compute, normalize, mem)
+                                      k_nearest_neighbors, compute, normalize, mem, deterministic)
     lib = _lib.load()
     ref, M0, C = _flat(reference_embeddings, "reference_embeddings")
     qry, N, C2 = _flat(query_embeddings, "query_embeddings")
@@ -634,12 +638,16 @@ def local_dist(x, y, max_distance, downsample=True):
 
 
 def local_match(prev_frame_embedding, query_embedding, prev_frame_labels, n_ids, max_distance=12,
-                downsample=True):
-    """local_previous_frame_nearest_neighbor_features_per_object (IntVOS.py:345-434) -> [h, w, n_ids]."""
+                downsample=True, deterministic=False):
+    """local_previous_frame_nearest_neighbor_features_per_object (IntVOS.py:345-434) -> [h, w, n_ids].
+    deterministic=True: when the call is differentiated, the ordered training route (csrc/match_train.hip): the same forward
+    bits, a sparse backward without float atomics (the same gradient bits on every run)."""
     import ctypes
     lib = _lib.load()
     if _wants_grad(prev_frame_embedding, query_embedding):
-        from .autograd import LocalMatchFn, LocalMatchFullFn
+        from .autograd import LocalMatchFn, LocalMatchFullFn, LocalMatchOrderedFn, LocalMatchFullOrderedFn
+        if deterministic:
+            LocalMatchFn, LocalMatchFullFn = LocalMatchOrderedFn, LocalMatchFullOrderedFn
         prev = _hwc(prev_frame_embedding, "prev_frame_embedding")
         cur = _hwc(query_embedding, "query_embedding")
         if tuple(prev.shape) != tuple(cur.shape):

@@ -664,6 +664,57 @@ int manet_local_match_full_backward_f32(const float *prev_chw, const float *cur_
                                         const float *grad_out, int h, int w, int C, int n_ids, int max_distance,
                                         float *grad_prev_chw, float *grad_cur_chw, float *dv_ws, manet_stream_t stream);
 
+/* The ordered training route of the matching path (csrc/match_train.hip): the same gradients as the four backward entry points
+ * above WITHOUT float atomics -- every sum has one owner that adds its terms in an order fixed by indices alone, so the result is
+ * the same bits on every run (the atomic route's last bits depend on arrival order).  Opt-in: ops.global_match / ops.local_match
+ * (deterministic=True), IntVOS(train_match="ordered").  The usual contract: raw pointers + element strides, int return, no
+ * allocation, no synchronisation, the caller's stream.
+ *
+ * manet_global_match_backward_ordered_f32 (reference IntVOS.py:32-39, :84, :87-94): arg / grad_weighted [ranks][N][n_ids], both
+ *   16-byte aligned; ranks = 1 for k = 1 (grad_weighted = grad_out), ranks = k for k = 2..8 (rank r's rows, -1 = none, and the
+ *   incoming gradient times that rank's weight): ALL ranks in one call.
+ *     grad_query[n] = sum_{r,o} 2 gw (q_n - k_m)                 (lane-local, ascending (r, o))
+ *     grad_bank[m]  = sum over the entries with arg = m of -2 gw (q_n - k_m), added by the owner of row m in ascending (r, n, o)
+ *   (both: a rank's terms into a sum of their own, the ranks' sums then added in ascending rank -- the association of one backward
+ *   per rank, so the rounding error is of the per-rank route's size)
+ *   Either gradient may be NULL: it costs nothing.  Workspace (needed for grad_bank only): the query as [N][C] rows,
+ *   align256(N * C * 4) bytes.
+ * manet_local_match_train_forward_f32: manet_local_match_arg_f32 -- same arguments, same workspace
+ *   (manet_local_match_arg_workspace_bytes), same bits in out / arg_out / vol_out -- with the masked minimum dealt to
+ *   (2d+1) x 2 threads per pixel instead of one thread's serial loop over the (2d+1)^2 candidates.
+ * manet_local_match_train_backward_f32 (IntVOS.py:266-296, :398-432; downsample configuration): manet_local_match_backward_f32's
+ *   arguments; grad_prev or grad_cur may be NULL (a frozen frame: no work for it).  Sparse: per pooled cell the winners among the
+ *   full-resolution pixels whose bilinear taps include it, in ascending (y, x, o); per destination cell of the previous frame the
+ *   window offsets in ascending order; no dense gradient volume.  Workspace, with hp = h/2, wp = w/2, cells = hp * wp and
+ *   cap = min((2d+1)^2, cover(h) * cover(w) * n_ids), cover(s) = the most positions of s whose two taps include one pooled
+ *   position (5 for every s in 12..480):
+ *     4 * align256(cells * C * 4) + align256(cells * 4) + 2 * align256(cells * cap * 4) + 2 * align256(cells * 20 * 4) bytes.
+ * manet_local_match_full_backward_ordered_f32 (IntVOS.py:299-313; MODEL_LOCAL_DOWNSAMPLE = False):
+ *   manet_local_match_full_backward_f32's arguments; one owner per (offset, pixel) adds the pixel's objects in ascending order;
+ *   grad_prev_chw or grad_cur_chw may be NULL. */
+int manet_global_match_backward_ordered_workspace_bytes(int64_t N, int64_t M0, int C, int n_ids, int ranks, size_t *bytes);
+int manet_global_match_backward_ordered_f32(const float *query, int64_t q_stride_n, int64_t q_stride_c, const float *bank,
+                                            int64_t b_stride_m, int64_t b_stride_c, const int32_t *arg,
+                                            const float *grad_weighted, int64_t N, int64_t M0, int C, int n_ids, int ranks,
+                                            float *grad_query, int64_t gq_stride_n, int64_t gq_stride_c, float *grad_bank,
+                                            int64_t gb_stride_m, int64_t gb_stride_c, void *workspace, size_t workspace_bytes,
+                                            manet_stream_t stream);
+int manet_local_match_train_forward_f32(const float *prev, int64_t p_sy, int64_t p_sx, int64_t p_sc, const float *cur,
+                                        int64_t c_sy, int64_t c_sx, int64_t c_sc, const int32_t *prev_labels, int h, int w,
+                                        int C, int n_ids, int max_distance, float *out, int32_t *arg_out, float *vol_out,
+                                        void *workspace, size_t workspace_bytes, manet_stream_t stream);
+int manet_local_match_train_workspace_bytes(int h, int w, int C, int n_ids, int max_distance, size_t *bytes);
+int manet_local_match_train_backward_f32(const float *prev, int64_t p_sy, int64_t p_sx, int64_t p_sc, const float *cur,
+                                         int64_t c_sy, int64_t c_sx, int64_t c_sc, const float *vol, const int32_t *arg,
+                                         const float *grad_out, int h, int w, int C, int n_ids, int max_distance,
+                                         float *grad_prev, int64_t gp_sy, int64_t gp_sx, int64_t gp_sc, float *grad_cur,
+                                         int64_t gc_sy, int64_t gc_sx, int64_t gc_sc, void *workspace, size_t workspace_bytes,
+                                         manet_stream_t stream);
+int manet_local_match_full_backward_ordered_f32(const float *prev_chw, const float *cur_chw, const int32_t *arg,
+                                                const float *grad_out, int h, int w, int C, int n_ids, int max_distance,
+                                                float *grad_prev_chw, float *grad_cur_chw, float *dv_ws,
+                                                manet_stream_t stream);
+
 /* correlation_package backward (correlation_cuda.cc:89-167): gradients w.r.t. both inputs,
  * [B][C][H][W] fp32 contiguous, fully overwritten. */
 int manet_correlation_backward_f32(const float *in1, const float *in2, const float *grad_out, int B,
