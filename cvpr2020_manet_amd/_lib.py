@@ -106,6 +106,9 @@ SIGNATURES = {
     "manet_local_volume_bytes": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_size_t)]),
     "manet_local_volume_frames": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "manet_local_match_volume": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    "manet_local_volume_bytes_f16": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_size_t)]),
+    "manet_local_volume_frames_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "manet_local_match_volume_f16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "manet_profile_read": (_i, [_i, ctypes.POINTER(ctypes.c_float), _i, _ip]),
     "manet_correlation_backward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "manet_correlation_backward_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -53,6 +53,7 @@ FLAGS = [
     #   MODEL_LOCAL_VOLUME_CACHE_MB  cap of the stored local-match volumes (IntVOS.prepare_local_volumes; LRU beyond it)
     #   MODEL_LOCAL_VOLUME_LAZY      store a frame pair's volume at its first use (no prepare_local_volumes call needed)
     #   MODEL_HEAD_MEMO_MB           cap of the heads' memoised layer-1 shared-half terms on the cached frames
+    #   MODEL_LOCAL_VOLUME_DTYPE     storage of the stored local-match volumes: f32 | f16 (OPTIONAL_FLAGS below)
     ("MODEL_MATCH_COMPUTE", S, "f32"), ("MODEL_EMB_DTYPE", S, "f32"), ("MODEL_HEAD_POINTWISE", S, "f32"),
     ("MODEL_CACHE_FRAMES", B, True), ("MODEL_LOCAL_VOLUME_CACHE_MB", I, 8192), ("MODEL_LOCAL_VOLUME_LAZY", B, False),
     ("MODEL_HEAD_MEMO_MB", I, 8192),
@@ -68,10 +69,17 @@ FLAGS = [
 ]
 
 
+# (flag, type) -- accepted on the command line, but an attribute of the cfg only when given: the default cfg keeps exactly the
+# attributes it had (IntVOS reads these with getattr: absent = the default, "f32" for MODEL_LOCAL_VOLUME_DTYPE)
+OPTIONAL_FLAGS = [("MODEL_LOCAL_VOLUME_DTYPE", S)]
+
+
 def build_parser():
     parser = argparse.ArgumentParser(description="intvos config", add_help=False)
     for name, kind, default in FLAGS:
         parser.add_argument("--" + name, type=kind, default=default)
+    for name, kind in OPTIONAL_FLAGS:
+        parser.add_argument("--" + name, type=kind, default=argparse.SUPPRESS)
     return parser
 
 

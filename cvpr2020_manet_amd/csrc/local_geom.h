@@ -92,10 +92,12 @@ constexpr int LF_NIP = 8;  // object ids per pass of the per-pixel phase
 // LDS of the per-pixel phase: the volume of `rows` window rows (padded to whole 1 KiB LDS-DMA pieces), the label bytes around the tile
 // for those rows, the per-(id, pixel) minima of `m2_rows` ids + the "no id" row, the bilinear tables, the label-change masks
 __host__ __device__ constexpr int lf_lab_rows_of(int d, int rows) { return 2 * (lf_sy(d) - 1) + 4 + 2 * (rows - 1); }
-__host__ __device__ constexpr size_t lf_vpad_bytes(int d, int rows) { return ((size_t)rows * lf_sy(d) * LF_SX * lf_vs(d) * 4 + 1023) / 1024 * 1024; }
-__host__ __device__ constexpr size_t lf_lds_phase2_bytes(int d, int rows, int m2_rows)
+// (es: bytes of a volume element -- 4, or 2 for the fp16 image of the stored volumes: the same [dy][cell][dx] order and cell stride
+// lf_vs(d) in elements, so a cell is 8 bytes times an odd number, a tap a ds_read_b64, and the region half as large)
+__host__ __device__ constexpr size_t lf_vpad_bytes(int d, int rows, size_t es = 4) { return ((size_t)rows * lf_sy(d) * LF_SX * lf_vs(d) * es + 1023) / 1024 * 1024; }
+__host__ __device__ constexpr size_t lf_lds_phase2_bytes(int d, int rows, int m2_rows, size_t es = 4)
 {
-    return lf_vpad_bytes(d, rows) + (((size_t)lf_lab_rows_of(d, rows) * lf_lab_cols(d) + 15) & ~(size_t)15) +
+    return lf_vpad_bytes(d, rows, es) + (((size_t)lf_lab_rows_of(d, rows) * lf_lab_cols(d) + 15) & ~(size_t)15) +
            (size_t)lf_npix(d) * (m2_rows + 1) * 4 + (size_t)(2 * (lf_sy(d) - 1) + 4 + 2 * (LF_SX - 1) + 4) * 16 +
            (size_t)lf_lab_rows_of(d, rows) * 16;
 }
@@ -103,7 +105,8 @@ __host__ __device__ constexpr size_t lf_lds_phase2_bytes(int d, int rows, int m2
 // lf_ndv(d) rows each (two or more then fit a CU).  Measured at 480p, d = 12 (docs/history/r06_experiments.md): 5 rows per workgroup
 // (one wave of 240 workgroups) 21.1 us; 2 rows (720 workgroups, two per CU) 23.8; 1 row (1 200, four per CU) 26-30 -- every
 // workgroup pays the label fetch, the tables, the minima's initialisation and the closing atomics again, and those, not the volume
-// stream, are what a workgroup waits for.  Shipped: no split (lf_ndv = lf_nd).
+// stream, are what a workgroup waits for.  Shipped: no split (lf_ndv = lf_nd).  The fp16 image keeps the split and the thread count
+// of the fp32 one (half the pieces per workgroup; the counted waits are derived from the piece count, not written down).
 #ifndef MANET_LF_NDV12
 #define MANET_LF_NDV12 5  // (A/B builds: window rows per workgroup of the stored-volume kernel at d = 12)
 #endif
@@ -113,9 +116,9 @@ __host__ __device__ constexpr size_t lf_lds_phase2_bytes(int d, int rows, int m2
 __host__ __device__ constexpr int lf_ndv(int d) { return d == 12 ? MANET_LF_NDV12 : lf_nd(d); }
 __host__ __device__ constexpr int lf_ntv(int d) { return (MANET_LF_NTV > 0 && d >= 10) ? MANET_LF_NTV : lf_nt(d); }
 __host__ __device__ constexpr int lf_nsub(int d) { return (lf_nd(d) + lf_ndv(d) - 1) / lf_ndv(d); }
-__host__ __device__ constexpr size_t lf_lds_vol_bytes(int d, int n_ids)
+__host__ __device__ constexpr size_t lf_lds_vol_bytes(int d, int n_ids, size_t es = 4)
 {
-    return lf_lds_phase2_bytes(d, lf_ndv(d), n_ids <= LF_NIP ? n_ids : LF_NIP);
+    return lf_lds_phase2_bytes(d, lf_ndv(d), n_ids <= LF_NIP ? n_ids : LF_NIP, es);
 }
 __host__ __device__ constexpr size_t lf_lds_bytes(int d)
 {

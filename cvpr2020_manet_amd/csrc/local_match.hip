@@ -442,22 +442,39 @@ __device__ __forceinline__ void lf_wait_vmcnt(int n)
 }
 // floats of one workgroup's volume image in memory: the LDS image padded to whole 1 KiB LDS-DMA pieces
 __host__ __device__ constexpr int lf_img_floats(int d) { return (lf_nd(d) * lf_sy(d) * LF_SX * lf_vs(d) + 255) / 256 * 256; }
-template <int D, int MODE>
-__global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__restrict__ curp_arg,
-                                                               const float *__restrict__ prevp_arg, int WS, long PS,
-                                                               const int *__restrict__ labels, int h, int w, int C,
-                                                               int n_ids, float *__restrict__ out,
-                                                               const int *__restrict__ tab, int abl_arg, int ntx, int nty,
-                                                               int rw, int rh, float *__restrict__ vol_arg,
-                                                               const typename std::conditional<MODE == LF_VOL_OUT, LfBatch,
-                                                                   typename std::conditional<MODE == LF_VOL_IN, LfTab, int>::type>::type batch)
+// The fp16 image (VT = _Float16, the opt-in storage type of the stored volumes): the SAME [dy][cell of S][dx] order and the same cell
+// stride lf_vs(d) counted in ELEMENTS -- 8 bytes times an odd number, a pixel's taps are ds_read_b64 of 4 window columns and the 16
+// cells of a row of S land on 16 distinct bank pairs.  In memory the images lie back to back WITHOUT the padding to whole pieces
+// (every image is a multiple of 128 bytes; the last piece of a workgroup's fetch reads into the next image, or into the 1 KiB
+// behind the last one, and lands in the padding of the LDS region): exactly half the bytes of the fp32 images' payload.
+template <typename VT>
+__host__ __device__ constexpr int lf_img_elems(int d)
 {
+    return sizeof(VT) == 4 ? lf_img_floats(d) : lf_nd(d) * lf_sy(d) * LF_SX * lf_vs(d);
+}
+typedef _Float16 lf_h4 __attribute__((ext_vector_type(4)));
+// four neighbouring window columns of one cell, widened to fp32 (exact)
+__device__ __forceinline__ f32x4 lf_tap4(const float *p) { return *(const f32x4 *)p; }
+__device__ __forceinline__ f32x4 lf_tap4(const _Float16 *p) { return __builtin_convertvector(*(const lf_h4 *)p, f32x4); }
+template <int MODE>
+using LfExtra = typename std::conditional<MODE == LF_VOL_OUT, LfBatch, typename std::conditional<MODE == LF_VOL_IN, LfTab, int>::type>::type;
+// The body of local_fused_kernel<D, MODE> (VT = float: the volume image as fp32, every mode) and of local_fused_f16_kernel<D, MODE>
+// (VT = _Float16: LF_VOL_OUT rounds each normalised distance once to IEEE half, to nearest even, subnormals kept; LF_VOL_IN widens
+// the taps back to fp32 and runs the same expression).
+template <int D, int MODE, typename VT>
+__device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, const float *__restrict__ prevp_arg, int WS, long PS,
+                                        const int *__restrict__ labels, int h, int w, int C, int n_ids, float *__restrict__ out,
+                                        const int *__restrict__ tab, int abl_arg, int ntx, int nty, int rw, int rh,
+                                        VT *__restrict__ vol_arg, const LfExtra<MODE> batch)
+{
+    static_assert(sizeof(VT) == 4 || MODE != LF_FUSED, "the fp16 image exists in memory only");
+    constexpr bool F16 = sizeof(VT) == 2;
     const float *curp = curp_arg, *prevp = prevp_arg;
-    float *vol = vol_arg;
+    VT *vol = vol_arg;
     if constexpr (MODE == LF_VOL_OUT) {
         curp = batch.cur[blockIdx.y];
         prevp = batch.prev[blockIdx.y];
-        vol = batch.vol[blockIdx.y];
+        vol = (VT *)batch.vol[blockIdx.y];
     }
     // (the ablation switch is a compile-time 0 outside -DMANET_ABLATION builds: no run-time tests in the loops)
 #ifdef MANET_ABLATION
@@ -495,8 +512,8 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
     // window rows this workgroup really owns (the last group of an image / the last image of a tile may hold fewer)
     const int nd_here = min(min(P - dy0, ND - sub * NDR), NDR);
     if (nd_here <= 0) return;
-    float *vimg = MODE == LF_FUSED ? nullptr
-                                   : vol + (long)((tiz * nty + tiy) * ntx + tix) * lf_img_floats(D) + (long)sub * NDR * (SY * LF_SX * lf_vs(D));
+    VT *vimg = MODE == LF_FUSED ? nullptr
+                                : vol + (long)((tiz * nty + tiy) * ntx + tix) * lf_img_elems<VT>(D) + (long)sub * NDR * (SY * LF_SX * lf_vs(D));
 
     // ---- phase 1: distances on S for window rows dy0 .. dy0+ND-1 ---------------------------------
     // Staging by LDS-DMA (lds_dma16: 64 lanes x 16 bytes land in 1 KiB of LDS, no VGPR hop, no ds_write): a stage is
@@ -654,8 +671,13 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
     // VR1 window rows -> their items; the rest -> the other items.  The launch is one wave of workgroups: without this every
     // workgroup waited 7 us for the whole 25.8 MB and then all of them computed (timeline in docs/history/r06_experiments.md).
     constexpr int VR1 = (2 * NDR) / 5 > 0 ? (2 * NDR) / 5 : 1;  // window rows whose items start first
-    constexpr int IMG_PIECES = (int)(lf_vpad_bytes(D, NDR) / 1024);  // (whole 1 KiB pieces: the tail lands in the V region's padding)
-    constexpr int IMG_P1 = NDR > VR1 ? (VR1 * SY * LF_SX * lf_vs(D) * 4 + 1023) / 1024 : IMG_PIECES;
+    constexpr int IMG_PIECES = (int)(lf_vpad_bytes(D, NDR, sizeof(VT)) / 1024);  // (whole 1 KiB pieces: the tail lands in the V region's padding)
+    // the fetch of an image's LAST row group ends at most 1 KiB behind the image: the slack manet_local_volume_bytes[_f16] adds behind
+    // the last image (true for lf_nsub = 1 and for any lf_ndv that divides lf_nd; a split that leaves a partial group would overrun)
+    static_assert(MODE != LF_VOL_IN || (size_t)(NSUB - 1) * NDR * SY * LF_SX * lf_vs(D) * sizeof(VT) + (size_t)IMG_PIECES * 1024 <=
+                                           (size_t)lf_img_elems<VT>(D) * sizeof(VT) + 1024,
+                  "the stored-volume tail would fetch past the volume's 1 KiB of slack");
+    constexpr int IMG_P1 = NDR > VR1 ? (VR1 * SY * LF_SX * lf_vs(D) * (int)sizeof(VT) + 1023) / 1024 : IMG_PIECES;
     // this wave's pieces among the first x pieces of the image (dealt round-robin)
     auto my_pieces = [&](int x) __attribute__((always_inline)) { return x > wave ? (x - wave + NWV - 1) / NWV : 0; };
     LF_T(1)
@@ -702,7 +724,7 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
         }
     }
     if constexpr (MODE == LF_VOL_IN) {
-        for (int pc = wave; pc < IMG_PIECES; pc += NWV) lds_dma16(vimg + (pc * 64 + lane) * 4, smem_base + (unsigned)pc * 1024u);
+        for (int pc = wave; pc < IMG_PIECES; pc += NWV) lds_dma16((const float *)vimg + (pc * 64 + lane) * 4, smem_base + (unsigned)pc * 1024u);
         lf_wait_vmcnt(my_pieces(IMG_PIECES));  // the label loads are older than this wave's pieces: they have landed
     }
     if constexpr (MODE == LF_VOL_IN) {
@@ -731,10 +753,10 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
 
     LF_T(2)
     constexpr int VS = lf_vs(D), NPS = lf_npix(D);
-    float *V = smem;                                                 // [NDR][SY * 16][VS] (+ the tail of the last LDS-DMA piece)
-    unsigned char *L = (unsigned char *)smem + lf_vpad_bytes(D, NDR);  // [lab_rows][lab_cols]; a byte >= the pass's ids = "no id"
+    VT *V = (VT *)smem;                                              // [NDR][SY * 16][VS] (+ the tail of the last LDS-DMA piece)
+    unsigned char *L = (unsigned char *)smem + lf_vpad_bytes(D, NDR, sizeof(VT));  // [lab_rows][lab_cols]; a byte >= the pass's ids = "no id"
     if (MODE != LF_VOL_IN && active) {
-        float *vp0 = V + ((dyi * SY + ry) * LF_SX + COLS * g) * VS + dx_lo;
+        VT *vp0 = V + ((dyi * SY + ry) * LF_SX + COLS * g) * VS + dx_lo;
 #pragma unroll
         for (int j = 0; j < COLS; ++j) {
 #pragma unroll
@@ -743,11 +765,12 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
                     f32x4 t;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) t[i] = (abl & 4) ? LF_ACC(j, d4 + i) : manet_normalize_dist_local(LF_ACC(j, d4 + i));
-                    *(f32x4 *)(vp0 + j * VS + d4) = t;
+                    if constexpr (F16) *(lf_h4 *)(vp0 + j * VS + d4) = __builtin_convertvector(t, lf_h4);  // v_cvt_f16_f32: to nearest even
+                    else *(f32x4 *)(vp0 + j * VS + d4) = t;
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        if (d4 + i < PA && d4 + i < ndx) vp0[j * VS + d4 + i] = manet_normalize_dist_local(LF_ACC(j, d4 + i));
+                        if (d4 + i < PA && d4 + i < ndx) vp0[j * VS + d4 + i] = (VT)manet_normalize_dist_local(LF_ACC(j, d4 + i));
                 }
             }
         }
@@ -757,7 +780,7 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
         // the image as phase 2 reads it, to memory in one linear pass (entries no thread wrote -- the cells' padding past the
         // window width, window rows past 2d+1 in the last group -- travel along and are never used)
         __syncthreads();
-        constexpr int IMG4 = ND * SY * LF_SX * VS / 4;
+        constexpr int IMG4 = ND * SY * LF_SX * VS * (int)sizeof(VT) / 16;
         for (int i = tid; i < IMG4; i += NT) ((f32x4 *)vimg)[i] = ((const f32x4 *)V)[i];
         return;
     }
@@ -822,8 +845,8 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
                 const int by = (int)(((float)item + 0.5f) * inv_npix), pix = item - by * npix;
                 const int py = (int)(((float)pix + 0.5f) * inv_nx), pxx = pix - py * nx;
                 const Tap r = RT[py], c = CT[pxx];
-                const float *vb = V + by * (SY * LF_SX * VS);
-                const float *p00 = vb + r.o0 + c.o0, *p01 = vb + r.o0 + c.o1, *p10 = vb + r.o1 + c.o0, *p11 = vb + r.o1 + c.o1;
+                const VT *vb = V + by * (SY * LF_SX * VS);
+                const VT *p00 = vb + r.o0 + c.o0, *p01 = vb + r.o0 + c.o1, *p10 = vb + r.o1 + c.o0, *p11 = vb + r.o1 + c.o1;
                 const unsigned char *lrow = L + (py + 2 * by) * lcols + pxx;
                 unsigned *mrow = M2 + pix;
                 const f32x2 cl0 = {c.l0, c.l0}, cl1 = {c.l1, c.l1}, rl0 = {r.l0, r.l0}, rl1 = {r.l1, r.l1};
@@ -836,8 +859,8 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
                         float m_ = INFINITY;
 #pragma unroll
                         for (int q = 0; q < (P + 3) / 4; ++q) {
-                            const f32x4 t00 = *(const f32x4 *)(p00 + 4 * q), t01 = *(const f32x4 *)(p01 + 4 * q);
-                            const f32x4 t10 = *(const f32x4 *)(p10 + 4 * q), t11 = *(const f32x4 *)(p11 + 4 * q);
+                            const f32x4 t00 = lf_tap4(p00 + 4 * q), t01 = lf_tap4(p01 + 4 * q);
+                            const f32x4 t10 = lf_tap4(p10 + 4 * q), t11 = lf_tap4(p11 + 4 * q);
 #pragma unroll
                             for (int i = 0; i < 4; i += 2) {
                                 if (4 * q + i >= P) continue;
@@ -858,8 +881,8 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
                 }
 #pragma unroll
                 for (int q = 0; q < (P + 3) / 4; ++q) {
-                    const f32x4 t00 = *(const f32x4 *)(p00 + 4 * q), t01 = *(const f32x4 *)(p01 + 4 * q);
-                    const f32x4 t10 = *(const f32x4 *)(p10 + 4 * q), t11 = *(const f32x4 *)(p11 + 4 * q);
+                    const f32x4 t00 = lf_tap4(p00 + 4 * q), t01 = lf_tap4(p01 + 4 * q);
+                    const f32x4 t10 = lf_tap4(p10 + 4 * q), t11 = lf_tap4(p11 + 4 * q);
 #pragma unroll
                     for (int i = 0; i < 4; i += 2) {
                         if (4 * q + i >= P) continue;
@@ -908,21 +931,52 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__re
     }
 }
 
-template <int D, int MODE = LF_FUSED>
+template <int D, int MODE>
+__global__ __launch_bounds__(lf_nt(D)) void local_fused_kernel(const float *__restrict__ curp_arg,
+                                                               const float *__restrict__ prevp_arg, int WS, long PS,
+                                                               const int *__restrict__ labels, int h, int w, int C,
+                                                               int n_ids, float *__restrict__ out,
+                                                               const int *__restrict__ tab, int abl_arg, int ntx, int nty,
+                                                               int rw, int rh, float *__restrict__ vol_arg,
+                                                               const LfExtra<MODE> batch)
+{
+    lf_body<D, MODE, float>(curp_arg, prevp_arg, WS, PS, labels, h, w, C, n_ids, out, tab, abl_arg, ntx, nty, rw, rh, vol_arg, batch);
+}
+// The two halves on an fp16 image (MODE = LF_VOL_OUT or LF_VOL_IN; the same arguments, the volume as _Float16)
+template <int D, int MODE>
+__global__ __launch_bounds__(lf_nt(D)) void local_fused_f16_kernel(const float *__restrict__ curp_arg,
+                                                                   const float *__restrict__ prevp_arg, int WS, long PS,
+                                                                   const int *__restrict__ labels, int h, int w, int C,
+                                                                   int n_ids, float *__restrict__ out,
+                                                                   const int *__restrict__ tab, int abl_arg, int ntx, int nty,
+                                                                   int rw, int rh, _Float16 *__restrict__ vol_arg,
+                                                                   const LfExtra<MODE> batch)
+{
+    static_assert(MODE == LF_VOL_OUT || MODE == LF_VOL_IN, "fp16 images are stored volumes");
+    static_assert(lf_ntv(D) <= lf_nt(D), "the launch bounds must cover the stored-volume tail's thread count");
+    lf_body<D, MODE, _Float16>(curp_arg, prevp_arg, WS, PS, labels, h, w, C, n_ids, out, tab, abl_arg, ntx, nty, rw, rh, vol_arg, batch);
+}
+
+template <int D, int MODE = LF_FUSED, typename VT = float>
 static void launch_fused_d(hipStream_t st, const float *ap, const float *bp, const PoolPad &G, const int *labels, int h,
-                           int w, int C, int n_ids, float *out, const int *tab, float *vol = nullptr,
+                           int w, int C, int n_ids, float *out, const int *tab, VT *vol = nullptr,
                            const LfBatch *batch = nullptr, int n_pairs = 1)
 {
+    // the kernel of this (mode, storage type)
+    constexpr auto kern = [] {
+        if constexpr (sizeof(VT) == 2) return local_fused_f16_kernel<D, MODE>;
+        else return local_fused_kernel<D, MODE>;
+    }();
     constexpr int TY = lf_sy(D) - 1, TX = LF_SX - 1;
     // i0 runs over 0..hp-1 (the last value only for the last row); tiles cover all of them
     const int ntx = (G.wp + TX - 1) / TX, nty = (G.hp + TY - 1) / TY;
     const int rw = (ntx + 3) / 4, rh = (nty + 1) / 2;  // tiles per XCD region (4 x 2 regions)
     dim3 grid((unsigned)(8 * rw * rh * lf_ndg(D) * (MODE == LF_VOL_IN ? lf_nsub(D) : 1)), (unsigned)(MODE == LF_VOL_OUT ? n_pairs : 1));
-    const size_t lds = MODE == LF_VOL_IN ? lf_lds_vol_bytes(D, n_ids) : lf_lds_bytes(D);
-    (void)hipFuncSetAttribute((const void *)local_fused_kernel<D, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(MODE == LF_VOL_IN ? lf_lds_vol_bytes(D, LF_NIP) : lds));
+    const size_t lds = MODE == LF_VOL_IN ? lf_lds_vol_bytes(D, n_ids, sizeof(VT)) : lf_lds_bytes(D);
+    (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(MODE == LF_VOL_IN ? lf_lds_vol_bytes(D, LF_NIP, sizeof(VT)) : lds));
     if constexpr (MODE == LF_VOL_OUT)
-        hipLaunchKernelGGL((local_fused_kernel<D, MODE>), grid, dim3(lf_nt(D)), lds, st, ap, bp, G.WS, G.plane, labels, h, w, C, n_ids,
+        hipLaunchKernelGGL(kern, grid, dim3(lf_nt(D)), lds, st, ap, bp, G.WS, G.plane, labels, h, w, C, n_ids,
                            out, tab, manet_tune_get(MANET_TUNE_ABLATION, 0), ntx, nty, rw, rh, vol, *batch);
     else if constexpr (MODE == LF_VOL_IN) {
         LfTab T;
@@ -932,10 +986,10 @@ static void launch_fused_d(hipStream_t st, const float *ap, const float *bp, con
             for (int i = 0; i <= nty; ++i) T.v[i] = bilin_first(i * TY, G.hp, h);
             for (int i = 0; i <= ntx; ++i) T.v[nty + 1 + i] = bilin_first(i * TX, G.wp, w);
         }
-        hipLaunchKernelGGL((local_fused_kernel<D, MODE>), grid, dim3(lf_ntv(D)), lds, st, ap, bp, G.WS, G.plane, labels, h, w, C, n_ids,
+        hipLaunchKernelGGL(kern, grid, dim3(lf_ntv(D)), lds, st, ap, bp, G.WS, G.plane, labels, h, w, C, n_ids,
                            out, tab, manet_tune_get(MANET_TUNE_ABLATION, 0), ntx, nty, rw, rh, vol, T);
     } else
-        hipLaunchKernelGGL((local_fused_kernel<D, MODE>), grid, dim3(lf_nt(D)), lds, st, ap, bp, G.WS,
+        hipLaunchKernelGGL(kern, grid, dim3(lf_nt(D)), lds, st, ap, bp, G.WS,
                            G.plane, labels, h, w, C, n_ids, out, tab, manet_tune_get(MANET_TUNE_ABLATION, 0), ntx, nty, rw, rh, vol, 0);
 }
 // workgroups (= volume images) of one frame pair
@@ -1335,21 +1389,33 @@ int manet_local_match_frames(const void *prev_frame_ws, const void *cur_frame_ws
 /* r6: the label-independent half of the local match, kept per frame pair (see local_fused_kernel's MODE).
  * manet_local_volume_bytes: bytes of one frame pair's normalised window-distance volume, stored as the per-workgroup LDS images
  * of the per-pixel phase (1.5x the bare (2d+1)^2 x h/2 x w/2 floats at d=12: tile aprons, 16-byte cell padding). */
-int manet_local_volume_bytes(int h, int w, int max_distance, size_t *bytes)
+extern "C++" {
+template <typename VT>
+static int local_volume_bytes_t(int h, int w, int max_distance, size_t *bytes)
 {
     if (!bytes) return manet_set_error(MANET_E_INVALID, "bytes == NULL");
     int rc = check_local(h, w, 1, max_distance, 1);
     if (rc) return rc;
     // (+ 1 KiB: the per-pixel kernel fetches a sub-group's rows in whole 1 KiB pieces and may read past the last image's end)
-    *bytes = (size_t)lf_images(h, w, max_distance) * lf_img_floats(max_distance) * sizeof(float) + 1024;
+    *bytes = (size_t)lf_images(h, w, max_distance) * lf_img_elems<VT>(max_distance) * sizeof(VT) + 1024;
     return MANET_OK;
+}
+}  // extern "C++"
+int manet_local_volume_bytes(int h, int w, int max_distance, size_t *bytes) { return local_volume_bytes_t<float>(h, w, max_distance, bytes); }
+/* The same volume with every normalised distance rounded once to IEEE half (to nearest even, subnormals kept; 1.0 stays 1.0): at
+ * most half the fp32 bytes plus one 1 KiB piece. */
+int manet_local_volume_bytes_f16(int h, int w, int max_distance, size_t *bytes)
+{
+    return local_volume_bytes_t<_Float16>(h, w, max_distance, bytes);
 }
 
 /* phase 1 (IntVOS.py:266-296) of n_pairs frame pairs, ceil(n_pairs / 32) launches: pair i = (prev_frame_ws[i], cur_frame_ws[i]),
  * two prepared frames (manet_frame_prepare) -> volumes[i] (manet_local_volume_bytes each, 16-byte aligned).  The three tables are
  * HOST arrays of device pointers. */
-int manet_local_volume_frames(const void *const *prev_frame_ws, const void *const *cur_frame_ws, float *const *volumes, int n_pairs,
-                              int h, int w, int C, int compute, int max_distance, manet_stream_t stream)
+extern "C++" {
+template <typename VT>
+static int local_volume_frames_t(const char *what, const void *const *prev_frame_ws, const void *const *cur_frame_ws, void *const *volumes,
+                                 int n_pairs, int h, int w, int C, int compute, int max_distance, manet_stream_t stream)
 {
     int rc = check_local(h, w, C, max_distance, 1);
     if (rc) return rc;
@@ -1368,10 +1434,10 @@ int manet_local_volume_frames(const void *const *prev_frame_ws, const void *cons
                 return manet_set_error(MANET_E_INVALID, "pair %d: null frame / volume pointer, or a volume not 16-byte aligned", j);
             B.cur[i] = (const float *)((const char *)cur_frame_ws[j] + F.off_plane);
             B.prev[i] = (const float *)((const char *)prev_frame_ws[j] + F.off_plane);
-            B.vol[i] = volumes[j];
+            B.vol[i] = (float *)volumes[j];  // (the kernel of the storage type reads it as VT)
         }
         const int *tab = (const int *)((const char *)cur_frame_ws[i0] + F.off_tab);  // (the same table for every frame of a geometry)
-#define MANET_LF_CASE(D_) case D_: launch_fused_d<D_, LF_VOL_OUT>(st, nullptr, nullptr, G, nullptr, h, w, C, 1, nullptr, tab, nullptr, &B, n); break;
+#define MANET_LF_CASE(D_) case D_: launch_fused_d<D_, LF_VOL_OUT, VT>(st, nullptr, nullptr, G, nullptr, h, w, C, 1, nullptr, tab, nullptr, &B, n); break;
         switch (max_distance) {
             MANET_LF_CASE(0) MANET_LF_CASE(1) MANET_LF_CASE(2) MANET_LF_CASE(3) MANET_LF_CASE(4) MANET_LF_CASE(5)
             MANET_LF_CASE(6) MANET_LF_CASE(7) MANET_LF_CASE(8) MANET_LF_CASE(9) MANET_LF_CASE(10) MANET_LF_CASE(11)
@@ -1380,14 +1446,31 @@ int manet_local_volume_frames(const void *const *prev_frame_ws, const void *cons
         }
 #undef MANET_LF_CASE
     }
-    return manet_check_launch("manet_local_volume_frames");
+    return manet_check_launch(what);
+}
+}  // extern "C++"
+int manet_local_volume_frames(const void *const *prev_frame_ws, const void *const *cur_frame_ws, float *const *volumes, int n_pairs,
+                              int h, int w, int C, int compute, int max_distance, manet_stream_t stream)
+{
+    return local_volume_frames_t<float>("manet_local_volume_frames", prev_frame_ws, cur_frame_ws, (void *const *)volumes, n_pairs, h, w,
+                                        C, compute, max_distance, stream);
+}
+/* ... into fp16 volumes (manet_local_volume_bytes_f16 each, 16-byte aligned): the same arithmetic up to and including the
+ * normalisation in fp32, then one conversion to half. */
+int manet_local_volume_frames_f16(const void *const *prev_frame_ws, const void *const *cur_frame_ws, void *const *volumes, int n_pairs,
+                                  int h, int w, int C, int compute, int max_distance, manet_stream_t stream)
+{
+    return local_volume_frames_t<_Float16>("manet_local_volume_frames_f16", prev_frame_ws, cur_frame_ws, volumes, n_pairs, h, w, C,
+                                           compute, max_distance, stream);
 }
 
 /* phase 2 (IntVOS.py:398-432) on a stored volume: bilinear taps + stride-2 label gather + masked minimum -> out [h][w][n_ids]; the
  * same bits as manet_local_match_frames on the pair the volume was made from.  cur_frame_ws: the current frame's prepared
  * workspace (its tile table). */
-int manet_local_match_volume(const float *volume, const void *cur_frame_ws, const int32_t *prev_labels, int h, int w, int C,
-                             int compute, int n_ids, int max_distance, float *out, int out_is_preset, manet_stream_t stream)
+extern "C++" {
+template <typename VT>
+static int local_match_volume_t(const char *what, const VT *volume, const void *cur_frame_ws, const int32_t *prev_labels, int h, int w,
+                                int C, int compute, int n_ids, int max_distance, float *out, int out_is_preset, manet_stream_t stream)
 {
     int rc = check_local(h, w, C, max_distance, 1);
     if (rc) return rc;
@@ -1407,7 +1490,7 @@ int manet_local_match_volume(const float *volume, const void *cur_frame_ws, cons
         if (blocks > 1024) blocks = 1024;
         hipLaunchKernelGGL(fill_f32_kernel, dim3(blocks), dim3(256), 0, st, out, 1.0f, n_out);
     }
-#define MANET_LF_CASE(D_) case D_: launch_fused_d<D_, LF_VOL_IN>(st, nullptr, nullptr, G, prev_labels, h, w, C, n_ids, out, tab, (float *)volume); break;
+#define MANET_LF_CASE(D_) case D_: launch_fused_d<D_, LF_VOL_IN, VT>(st, nullptr, nullptr, G, prev_labels, h, w, C, n_ids, out, tab, (VT *)volume); break;
     switch (max_distance) {
         MANET_LF_CASE(0) MANET_LF_CASE(1) MANET_LF_CASE(2) MANET_LF_CASE(3) MANET_LF_CASE(4) MANET_LF_CASE(5)
         MANET_LF_CASE(6) MANET_LF_CASE(7) MANET_LF_CASE(8) MANET_LF_CASE(9) MANET_LF_CASE(10) MANET_LF_CASE(11)
@@ -1416,7 +1499,22 @@ int manet_local_match_volume(const float *volume, const void *cur_frame_ws, cons
     }
 #undef MANET_LF_CASE
     manet_profile_record(st, false, 1);
-    return manet_check_launch("manet_local_match_volume");
+    return manet_check_launch(what);
+}
+}  // extern "C++"
+int manet_local_match_volume(const float *volume, const void *cur_frame_ws, const int32_t *prev_labels, int h, int w, int C,
+                             int compute, int n_ids, int max_distance, float *out, int out_is_preset, manet_stream_t stream)
+{
+    return local_match_volume_t<float>("manet_local_match_volume", volume, cur_frame_ws, prev_labels, h, w, C, compute, n_ids,
+                                       max_distance, out, out_is_preset, stream);
+}
+/* ... on an fp16 volume: the taps widened to fp32 (exact), then the same expression, label handling and out_is_preset protocol.
+ * Against the fp32 route |out_f16 - out_f32| <= min(2^-12, 2^-11 out_f32); an entry that is 1.0 stays 1.0. */
+int manet_local_match_volume_f16(const void *volume, const void *cur_frame_ws, const int32_t *prev_labels, int h, int w, int C,
+                                 int compute, int n_ids, int max_distance, float *out, int out_is_preset, manet_stream_t stream)
+{
+    return local_match_volume_t<_Float16>("manet_local_match_volume_f16", (const _Float16 *)volume, cur_frame_ws, prev_labels, h, w,
+                                          C, compute, n_ids, max_distance, out, out_is_preset, stream);
 }
 
 /* training path: downsample configuration only (the reference's live default, config.py:49) */

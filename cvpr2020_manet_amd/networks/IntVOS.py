@@ -176,6 +176,16 @@ def _train_match_mode(value):
     return value
 
 
+_VOLUME_DTYPES = {"f32": torch.float32, "f16": torch.float16}
+
+
+def _volume_dtype_mode(value):
+    mode = value.lower() if isinstance(value, str) else value
+    if mode not in _VOLUME_DTYPES:
+        raise ValueError("local_volume_dtype=%r ('f32' or 'f16')" % (value,))
+    return mode
+
+
 def _match_route(train_match):
     """keyword of ops.global_match / ops.local_match for a route (None: the module's TRAIN_MATCH); the default route calls the
     ops exactly as before"""
@@ -595,7 +605,7 @@ class IntVOS(nn.Module):
     """reference IntVOS.py:530-764: same constructor, methods, dict conventions, state-dict keys."""
 
     def __init__(self, cfg, feature_extracter, compute=None, emb_dtype=None, pointwise=None, cache_frames=None,
-                 train_kernels=None, train_match=None):
+                 train_kernels=None, train_match=None, local_volume_dtype=None):
         """cfg, feature_extracter: as the reference.  The rest is optional and this implementation's only (default: the
         cfg's MODEL_MATCH_COMPUTE / MODEL_EMB_DTYPE / MODEL_HEAD_POINTWISE / MODEL_CACHE_FRAMES when it has them, else
         "f32" / "f32" / "f32" / True):
@@ -617,7 +627,13 @@ class IntVOS(nn.Module):
                         it) the float-atomicAdd scatter -- the gradient that reaches the embedding head and the encoder can differ
                         in its last bits from run to run; "ordered" the atomic-free kernels of csrc/match_train.hip: the same bits
                         on every run (with train_kernels="fused" and the fused loss the whole step behind the encoder is
-                        reproducible), a sparse local backward and a faster training forward of the local match"""
+                        reproducible), a sparse local backward and a faster training forward of the local match
+          local_volume_dtype  storage type of the stored local-match volumes (prepare_local_volumes, the lazy path, the
+                        interaction head's self-match): "f32" (default; cfg's MODEL_LOCAL_VOLUME_DTYPE when it has it) the same
+                        bits as the fused kernel | "f16" every normalised window distance rounded once to half: half the bytes,
+                        twice the pairs under `local_volume_cache_bytes`; a local map then differs from the "f32" one by at most
+                        min(2^-12, 2^-11 * value), and 1.0 stays 1.0.  Readable and assignable (`model.local_volume_dtype`);
+                        assigning another value drops the cached volumes"""
         super().__init__()
         set_cfg(cfg)
         self.cfg = cfg
@@ -662,6 +678,9 @@ class IntVOS(nn.Module):
         self._vol_cache_bytes = 0
         self.local_volume_cache_bytes = int(getattr(cfg, "MODEL_LOCAL_VOLUME_CACHE_MB", DEFAULT_LOCAL_VOLUME_CACHE_MB)) << 20
         self.local_volume_lazy = bool(getattr(cfg, "MODEL_LOCAL_VOLUME_LAZY", False))
+        # (a plain attribute: not a buffer, not in the state dict)
+        self._local_volume_dtype = _volume_dtype_mode(
+            local_volume_dtype if local_volume_dtype is not None else getattr(cfg, "MODEL_LOCAL_VOLUME_DTYPE", "f32"))
         self.dynamic_seghead = DynamicSegHead()  # propagation head
         if cfg.MODEL_USEIntSeg:
             self.inter_seghead = IntSegHead(in_dim=cfg.MODEL_SEMANTIC_EMBEDDING_DIM + 3)
@@ -675,6 +694,18 @@ class IntVOS(nn.Module):
         use_train_kernels(self, self.train_kernels)
         # (a plain attribute: not a buffer, not in the state dict)
         self.train_match = _train_match_mode(train_match if train_match is not None else getattr(cfg, "MODEL_TRAIN_MATCH", "atomic"))
+
+    @property
+    def local_volume_dtype(self):
+        """ "f32" or "f16": the storage type of the stored local-match volumes (see the constructor)"""
+        return self._local_volume_dtype
+
+    @local_volume_dtype.setter
+    def local_volume_dtype(self, value):
+        mode = _volume_dtype_mode(value)
+        if mode != self._local_volume_dtype:
+            self.invalidate_local_volumes()  # one cache never mixes storage types
+        self._local_volume_dtype = mode
 
     def _prepared_bank(self, seq_name, ref_emb_chw, ref_label, ref_emb_hwc, ref_lab_flat, n_ids):
         """The sorted / packed memory bank of the annotated frame, reused while the caller keeps passing the SAME
@@ -908,17 +939,19 @@ class IntVOS(nn.Module):
         if not todo:
             return hits
         h, w = todo[0][3].shape[-2:]
-        per = ops.local_volume_bytes(int(h), int(w), d)
+        vdt = _VOLUME_DTYPES[self._local_volume_dtype]
+        per = ops.local_volume_bytes(int(h), int(w), d, vdt)
         todo = todo[:max(0, self.local_volume_cache_bytes // per)]  # what does not fit the cap stays on the fused kernel
         if not todo:
             return hits
+        store_es = 4 if vdt == torch.float32 else 2
         # ONE allocation for the call's volumes (a first-time device allocation of this size costs milliseconds: once, not per batch)
-        store = torch.empty((len(todo), per // 4), dtype=torch.float32, device=todo[0][3].device)
+        store = torch.empty((len(todo), per // store_es), dtype=vdt, device=todo[0][3].device)
         for i0 in range(0, len(todo), batch):
             part = todo[i0:i0 + batch]
             prevs = [self._prepared_frame(ep)[0] for (_, _, ep, _) in part]
             curs = [self._prepared_frame(ec)[0] for (_, _, _, ec) in part]
-            vols = ops.local_volumes(prevs, curs, out=store[i0:i0 + len(part)])
+            vols = ops.local_volumes(prevs, curs, out=store[i0:i0 + len(part)], dtype=vdt)
             for j, (kp, kc, ep, ec) in enumerate(part):
                 self._vol_store((kp, kc), vols[j], ep, ec)
         return hits + len(todo)
@@ -933,10 +966,10 @@ class IntVOS(nn.Module):
     def _vol_store(self, key, vol, ep, ec):
         # (the keys hold storage pointers: the embeddings stay alive with the entry)
         self._vol_cache[key] = [vol, ep, ec]
-        self._vol_cache_bytes += vol.numel() * 4
+        self._vol_cache_bytes += vol.numel() * vol.element_size()
         while self._vol_cache_bytes > self.local_volume_cache_bytes and len(self._vol_cache) > 1:
             _, old = self._vol_cache.popitem(last=False)
-            self._vol_cache_bytes -= old[0].numel() * 4
+            self._vol_cache_bytes -= old[0].numel() * old[0].element_size()
 
     def _local_volume(self, prev_chw, cur_chw, fcur=None):
         """the stored volume of (previous frame, current frame), or None (then the fused kernel runs).  With
@@ -956,7 +989,7 @@ class IntVOS(nn.Module):
             return None
         fprev = self._prepared_frame(prev_chw)[0]
         fcur = fcur if fcur is not None else self._prepared_frame(cur_chw)[0]
-        vol = ops.local_volumes([fprev], [fcur])[0]
+        vol = ops.local_volumes([fprev], [fcur], dtype=_VOLUME_DTYPES[self._local_volume_dtype])[0]
         self._vol_store((kp, kc), vol, prev_chw, cur_chw)
         return vol
 

@@ -513,26 +513,41 @@ def local_match_frames(prev_frame, cur_frame, prev_frame_labels, n_ids, out=None
     return out.view(b.h, b.w, n_ids)
 
 
-def local_volume_bytes(h, w, max_distance):
-    """bytes of one frame pair's stored window-distance volume (manet_local_volume_bytes)"""
+_VOLUME_SUFFIX = {torch.float32: "", torch.float16: "_f16"}
+
+
+def _volume_suffix(dtype):
+    try:
+        return _VOLUME_SUFFIX[dtype]
+    except KeyError:
+        raise ValueError("stored volumes are torch.float32 or torch.float16, not %r" % (dtype,)) from None
+
+
+def local_volume_bytes(h, w, max_distance, dtype=torch.float32):
+    """bytes of one frame pair's stored window-distance volume (manet_local_volume_bytes; torch.float16: the half-precision
+    storage type, manet_local_volume_bytes_f16 -- at most half the fp32 bytes plus one 1 KiB piece)"""
     import ctypes
+    name = "manet_local_volume_bytes" + _volume_suffix(dtype)
     nbytes = ctypes.c_size_t(0)
-    _lib.check(_lib.load().manet_local_volume_bytes(h, w, max_distance, ctypes.byref(nbytes)), "manet_local_volume_bytes")
+    _lib.check(getattr(_lib.load(), name)(h, w, max_distance, ctypes.byref(nbytes)), name)
     return nbytes.value
 
 
-def local_volumes(prev_frames, cur_frames, out=None):
+def local_volumes(prev_frames, cur_frames, out=None, dtype=torch.float32):
     """The label-independent half of the local match (IntVOS.py:266-296: pooled frames -> (2d+1)^2 window distances ->
     (sigmoid - 0.5) * 2) for a BATCH of frame pairs (prev_frames[i], cur_frames[i]) -- lists of PreparedFrames of one geometry --
-    in ceil(n / 32) launches.  Returns a float32 tensor [n, floats per volume]; row i feeds local_match_volume.  `out`: an
-    optional contiguous float32 tensor of that shape to write into."""
+    in ceil(n / 32) launches.  Returns a `dtype` tensor [n, elements per volume]; row i feeds local_match_volume.  `out`: an
+    optional contiguous tensor of that dtype and shape to write into.  dtype=torch.float16 (opt-in): the fp32 arithmetic, then
+    every distance rounded once to half (to nearest even) -- half the bytes; local_match_volume on such a row stays within
+    min(2^-12, 2^-11 * value) of the float32 route."""
     import ctypes
     lib = _lib.load()
+    sfx = _volume_suffix(dtype)
     n = len(cur_frames)
     if len(prev_frames) != n:
         raise ValueError("prev_frames and cur_frames must pair up")
     if n == 0:
-        return torch.empty((0, 0), dtype=torch.float32)
+        return torch.empty((0, 0), dtype=dtype)
     b = cur_frames[0]
     for a in list(prev_frames) + list(cur_frames):
         if (a.h, a.w, a.C, _image_kind(a.compute), a.max_distance, a.device) != (b.h, b.w, b.C, _image_kind(b.compute),
@@ -540,31 +555,36 @@ def local_volumes(prev_frames, cur_frames, out=None):
             raise ValueError("the frames were prepared for different shapes / arithmetic / window radius / devices")
     if b.max_distance < 0:
         raise ValueError("the frames were prepared without a pooled plane (max_distance < 0)")
-    per = local_volume_bytes(b.h, b.w, b.max_distance) // 4
+    es = 4 if dtype == torch.float32 else 2
+    per = local_volume_bytes(b.h, b.w, b.max_distance, dtype) // es
     if out is None:
-        out = torch.empty((n, per), dtype=torch.float32, device=b.device)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != (n, per) or out.device != b.device:
-        raise ValueError("out must be a contiguous float32 [%d, %d] tensor on the frames' device" % (n, per))
+        out = torch.empty((n, per), dtype=dtype, device=b.device)
+    elif out.dtype != dtype or not out.is_contiguous() or tuple(out.shape) != (n, per) or out.device != b.device:
+        raise ValueError("out must be a contiguous %s [%d, %d] tensor on the frames' device"
+                         % (str(dtype).replace("torch.", ""), n, per))
     arr = ctypes.c_void_p * n
     pv = arr(*[f.ws.data_ptr() for f in prev_frames])
     cv = arr(*[f.ws.data_ptr() for f in cur_frames])
     vv = arr(*[out[i].data_ptr() for i in range(n)])
+    name = "manet_local_volume_frames" + sfx
     with _on(b.device):
-        rc = lib.manet_local_volume_frames(pv, cv, vv, n, b.h, b.w, b.C, b.compute, b.max_distance, _stream_ptr(b.device))
-    _lib.check(rc, "manet_local_volume_frames")
+        rc = getattr(lib, name)(pv, cv, vv, n, b.h, b.w, b.C, b.compute, b.max_distance, _stream_ptr(b.device))
+    _lib.check(rc, name)
     return out
 
 
 def local_match_volume(volume, cur_frame, prev_frame_labels, n_ids, out=None, out_is_preset=False):
     """The label-dependent tail of the local match (IntVOS.py:398-432) on a stored volume (one row of local_volumes) -> [h, w,
-    n_ids]; bit-identical to local_match_frames(prev_frame, cur_frame, ...) on the pair the volume was made from."""
+    n_ids]; on a float32 row bit-identical to local_match_frames(prev_frame, cur_frame, ...) on the pair the volume was made
+    from, on a float16 row (dispatch on volume.dtype) bit-identical to this function on the float32 row rounded to half."""
     lib = _lib.load()
     b = cur_frame
     if b.max_distance < 0:
         raise ValueError("the frame was prepared without a pooled plane (max_distance < 0)")
-    if (volume.dtype != torch.float32 or not volume.is_contiguous() or volume.device != b.device
-            or volume.numel() * 4 != local_volume_bytes(b.h, b.w, b.max_distance)):
-        raise ValueError("volume must be one contiguous float32 row of local_volumes() for this frame geometry")
+    if (volume.dtype not in _VOLUME_SUFFIX or not volume.is_contiguous() or volume.device != b.device
+            or volume.numel() * volume.element_size() != local_volume_bytes(b.h, b.w, b.max_distance, volume.dtype)):
+        raise ValueError("volume must be one contiguous float32 (or float16) row of local_volumes() for this frame geometry")
+    name = "manet_local_match_volume" + _VOLUME_SUFFIX[volume.dtype]
     lab = _labels(prev_frame_labels, "prev_frame_labels")
     if lab.numel() != b.h * b.w:
         raise ValueError("prev_frame_labels must have height*width entries")
@@ -575,9 +595,9 @@ def local_match_volume(volume, cur_frame, prev_frame_labels, n_ids, out=None, ou
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != b.h * b.w * n_ids:
         raise ValueError("out must be a contiguous float32 tensor of h*w*n_ids elements")
     with _on(dev):
-        rc = lib.manet_local_match_volume(volume.data_ptr(), b.ws.data_ptr(), lab.data_ptr(), b.h, b.w, b.C, b.compute, n_ids,
-                                          b.max_distance, out.data_ptr(), int(bool(out_is_preset)), _stream_ptr(dev))
-    _lib.check(rc, "manet_local_match_volume")
+        rc = getattr(lib, name)(volume.data_ptr(), b.ws.data_ptr(), lab.data_ptr(), b.h, b.w, b.C, b.compute, n_ids,
+                                b.max_distance, out.data_ptr(), int(bool(out_is_preset)), _stream_ptr(dev))
+    _lib.check(rc, name)
     return out.view(b.h, b.w, n_ids)
 
 

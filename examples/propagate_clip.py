@@ -66,13 +66,13 @@ class StandInEncoder(nn.Module):
         return self.net(x)
 
 
-def build_model(dev, compute=None, emb_dtype=None, pointwise=None, seed=0):
+def build_model(dev, compute=None, emb_dtype=None, pointwise=None, seed=0, local_volume_dtype=None):
     from cvpr2020_manet_amd.config import make_cfg
     from cvpr2020_manet_amd.networks.IntVOS import IntVOS
     torch.manual_seed(seed)
     cfg = make_cfg(["--TEST_MODE", "True"])
     model = IntVOS(cfg, StandInEncoder(cfg.MODEL_ASPP_OUTDIM), compute=compute, emb_dtype=emb_dtype,
-                   pointwise=pointwise).to(dev).eval()
+                   pointwise=pointwise, local_volume_dtype=local_volume_dtype).to(dev).eval()
     return cfg, model
 
 
@@ -314,7 +314,7 @@ class Clip:
             return masks
         return torch.cat([masks[i][0] for i in range(self.F)], 0)
 
-    def session(self, n_rounds, timed=True):
+    def session(self, n_rounds, timed=True, keep_logits=None):
         """An interactive SESSION as test.py:100-310 runs it: `n_rounds` interaction rounds on one sequence with the memories
         carried over.  Round 1: scribbles on the middle frame, `rough_ROI` bank (test.py:229-230).  Round r > 1: new scribbles on
         another frame, the interaction head also sees the previous round's mask of that frame (first_inter=False,
@@ -349,6 +349,8 @@ class Clip:
                                                           global_map_tmp_dic=gmap, local_map_dics=lmaps, interaction_num=r,
                                                           start_annotated_frame=start, frame_num=[ii],
                                                           dynamic_seghead=model.dynamic_seghead)
+                    if keep_logits is not None:
+                        keep_logits[(r, ii)] = tmp[SEQ].clone()
                     prev_label = self.mask_step(tmp[SEQ]).unsqueeze(0)
                     prev_emb = cur
                     storage[ii] = prev_label[0, 0]
@@ -479,9 +481,37 @@ def mask_digest(masks):
     return hashlib.sha256(masks.to(torch.int16).cpu().numpy().tobytes()).hexdigest()[:16]
 
 
+def against_f32_volumes(model, clip, emb, session=0):
+    """The same clip in the same process on fp32 volumes: what the rounded window distances move behind the head, over one
+    interaction round (every propagated frame) and, with `session`, over every frame of every round of that session.  A
+    measurement of THIS encoder's embeddings (a stand-in here): the local maps themselves are bounded (min(2^-12, 2^-11 * value)),
+    nothing bounds logits.  Runs after the timed regions; leaves the model in its own storage type with no volumes stored."""
+    def run():
+        logits = {}
+        masks = [clip.one_round(keep_logits=logits)]
+        if session:
+            masks.append(clip.session(session, timed=False, keep_logits=logits)[0])
+        return logits, masks
+
+    model.prepare_local_volumes(emb)  # (every pair of both directions: a no-op where they are stored already)
+    got, got_masks = run()
+    mode = model.local_volume_dtype
+    model.local_volume_dtype = "f32"  # (drops the cached volumes)
+    model.prepare_local_volumes(emb)
+    want, want_masks = run()
+    model.local_volume_dtype = mode
+    out = {"logit_max_abs_diff": max(float((got[k] - want[k]).abs().max()) for k in want if not isinstance(k, tuple)),
+           "mask_flip_fraction": float((got_masks[0] != want_masks[0]).float().mean())}
+    if session:
+        out.update({"session_logit_max_abs_diff": max(float((got[k] - want[k]).abs().max()) for k in want if isinstance(k, tuple)),
+                    "session_mask_flip_fraction": float((got_masks[1] != want_masks[1]).float().mean())})
+    return out
+
+
 def run_single(args, dev, pointwise=None, want_graph=False, want_stages=False, bank=None, bank_frames=None):
     """one process, one GPU: eager (and graph) frames/s of the end-to-end propagated frame"""
-    cfg, model = build_model(dev, args.compute, args.emb_dtype, pointwise if pointwise is not None else args.pointwise)
+    cfg, model = build_model(dev, args.compute, args.emb_dtype, pointwise if pointwise is not None else args.pointwise,
+                             local_volume_dtype=getattr(args, "volume_dtype", None))
     with torch.no_grad():
         # (the producer's fused epilogue: embeddings + every frame's operands from one launch per extraction batch)
         emb = synthetic_clip(model, dev, args.frames, args.height, args.width, args.objects, packed=not args.no_packed)
@@ -514,7 +544,7 @@ def run_single(args, dev, pointwise=None, want_graph=False, want_stages=False, b
                "compute": model.compute, "bank": clip.bank, "bank_frames": clip.bank_frames, "bank_rows": clip.bank_rows,
                "eager_ms_per_round": dt * 1e3, "eager_frames_per_s": (args.frames - 1) / dt,
                "local_volumes": {"pairs": vol_pairs, "head_term_frames": term_frames, "ms": vol_ms,
-                                 "MB": model.local_volume_bytes_cached() / 1e6},
+                                 "MB": model.local_volume_bytes_cached() / 1e6, "dtype": model.local_volume_dtype},
                "first_round_frames_per_s": (args.frames - 1) / (dt + vol_ms * 1e-3),
                "mask_digest": mask_digest(final)}
         if want_stages:
@@ -551,13 +581,16 @@ def run_single(args, dev, pointwise=None, want_graph=False, want_stages=False, b
             gdt = (time.perf_counter() - t0) / args.rounds
             res.update({"graph_ms_per_round": gdt * 1e3, "graph_frames_per_s": (args.frames - 1) / gdt,
                         "graph_masks_equal_eager": bool(torch.equal(gfinal, final))})
+        if model.local_volume_dtype != "f32" and vol_pairs:
+            res["local_volumes"].update(against_f32_volumes(model, clip, emb, session=getattr(args, "session", 0)))
     return res, clip, final
 
 
 def run_parallel(args, dev, rank, world):
     """clip-parallel propagation (module docstring): returns rank 0's result dict (None elsewhere)"""
     from cvpr2020_manet_amd import clip_parallel as cp
-    cfg, model = build_model(dev, args.compute, args.emb_dtype, args.pointwise)
+    cfg, model = build_model(dev, args.compute, args.emb_dtype, args.pointwise,
+                             local_volume_dtype=getattr(args, "volume_dtype", None))
     F_ = args.frames
     s0, e0 = cp.shard_frames(F_, world, rank)
     with torch.no_grad():
@@ -664,6 +697,9 @@ def run_parallel(args, dev, rank, world):
                      "amdahl_ceiling": (sharded_us + chain_us) / max(chain_us, 1e-9) * len(chain_ranks),
                      "measured_speedup": dt1 / dt})
         timing["gather"] = coll
+        vol_mb, vol_diff = model.local_volume_bytes_cached() / 1e6, {}
+        if model.local_volume_dtype != "f32" and not getattr(args, "no_local_volumes", False):
+            vol_diff = against_f32_volumes(model, clip, emb)  # (the 1-rank loop: the parallel round's masks are its bits)
         return {"frames": F_, "world": world, "backend": dist.get_backend(), "pointwise": model.pointwise,
                 "compute": model.compute, "bank": clip.bank, "bank_frames": clip.bank_frames, "bank_rows": clip.bank_rows,
                 "parallel_ms_per_round": dt * 1e3, "parallel_frames_per_s": (F_ - 1) / dt,
@@ -671,7 +707,8 @@ def run_parallel(args, dev, rank, world):
                 "masks_bit_equal_to_single_rank": same, "mask_digest": mask_digest(final),
                 "chain_ranks": list(chain_ranks),
                 "clip_all_gather_ms": clip_gather_ms, "rank0_global_maps_ms": timing.get("global_maps_ms"),
-                "rank0_local_volumes_ms": vol_ms, "rank0_local_volume_MB": model.local_volume_bytes_cached() / 1e6,
+                "rank0_local_volumes_ms": vol_ms, "rank0_local_volume_MB": vol_mb,
+                "local_volume_dtype": model.local_volume_dtype, "local_volumes": dict(vol_diff, dtype=model.local_volume_dtype),
                 "collective": timing.get("gather")}
 
 
@@ -721,6 +758,11 @@ def parse_args(argv=None):
     ap.add_argument("--no-local-volumes", action="store_true",
                     help="do not store the frame pairs' window-distance volumes up front (model.prepare_local_volumes): every "
                          "propagated frame then runs the fused local kernel, as r1-r5")
+    ap.add_argument("--volume-dtype", type=str, default=None, choices=["f32", "f16"],
+                    help="storage type of the stored window-distance volumes (model.local_volume_dtype): f16 = half the bytes, "
+                         "local maps within min(2^-12, 2^-11 * value) of f32's.  An f16 run also repeats the round (and the --session) "
+                         "on f32 volumes after the timed regions, for logit_max_abs_diff / mask_flip_fraction: about twice the "
+                         "wall time, the timed figures are not touched")
     ap.add_argument("--two-streams", action="store_true",
                     help="also time the round with the forward and the backward half of the chain on two HIP streams")
     ap.add_argument("--stages", action="store_true", help="per-stage microseconds of a propagated frame (HIP events)")

@@ -304,6 +304,22 @@ int manet_local_volume_frames(const void *const *prev_frame_ws, const void *cons
 int manet_local_match_volume(const float *volume, const void *cur_frame_ws, const int32_t *prev_labels, int h, int w, int C,
                              int compute, int n_ids, int max_distance, float *out, int out_is_preset, manet_stream_t stream);
 
+/* The same three with the volume stored as IEEE half (opt-in; the functions above keep their signatures and bits).  A frame pair
+ * costs at most half the fp32 bytes plus one 1 KiB piece (12.9 MB per 480p pair at d = 12): the images keep the fp32 order and the
+ * cell stride counted in elements, and lie back to back in memory.  Arguments, checks and error codes are those of the fp32
+ * functions (max_distance > 12: MANET_E_INVALID); `volumes` / `volume` point to manet_local_volume_bytes_f16 bytes each, 16-byte aligned.
+ * Numerical contract.  manet_local_volume_frames_f16 runs the fp32 arithmetic up to and including the normalisation
+ * (sigmoid(d) - 0.5) * 2, then rounds ONCE to half, to nearest even, subnormals kept; 1.0 (out of the image, saturated) stays 1.0.
+ * manet_local_match_volume_f16 widens the taps to fp32 exactly and evaluates the fp32 tail's expression in the same association:
+ * its result equals manet_local_match_volume on the fp32 volume rounded to half and widened again, bit for bit.  The stored values
+ * lie in [0, 1], the bilinear sample is a convex combination of four taps and the masked minimum is 1-Lipschitz, so against the
+ * fp32 route |out_f16 - out_f32| <= min(2^-12, 2^-11 * out_f32), and an entry that is 1.0 stays exactly 1.0. */
+int manet_local_volume_bytes_f16(int h, int w, int max_distance, size_t *bytes);
+int manet_local_volume_frames_f16(const void *const *prev_frame_ws, const void *const *cur_frame_ws, void *const *volumes,
+                                  int n_pairs, int h, int w, int C, int compute, int max_distance, manet_stream_t stream);
+int manet_local_match_volume_f16(const void *volume, const void *cur_frame_ws, const int32_t *prev_labels, int h, int w, int C,
+                                 int compute, int n_ids, int max_distance, float *out, int out_is_preset, manet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* correlation_package forward (correlation_cuda.cc:10-87).
  *   in1, in2 [B][C][H][W] fp32 contiguous; out [B][(2r+1)^2][outH][outW] fp32 contiguous with
