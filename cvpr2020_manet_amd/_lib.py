@@ -1,6 +1,7 @@
 """ctypes binding of libmanet_hip.so -- the C ABI declared in include/manet_hip.h.
 
-There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.
+There is no fallback: if the library is missing or a call fails, a RuntimeError is raised.  ops.py and autograd.py reach every
+entry point through `call` (call + check) and `query` (the same for entry points with output parameters: the `*_bytes` queries).
 """
 import ctypes
 import os
@@ -171,3 +172,21 @@ def check(rc, what):
     if rc != 0:
         msg = load().manet_last_error_string().decode("utf-8", "replace")
         raise RuntimeError("%s failed (code %d): %s" % (what, rc, msg))
+
+
+def call(fn, *args):
+    """Call an int-returning entry point -- its name, or the function object `load().manet_x` -- and raise through `check`
+    under the name of the symbol that was called."""
+    if isinstance(fn, str):
+        fn = getattr(_lib or load(), fn)
+    rc = fn(*args)
+    if rc:
+        check(rc, fn.__name__)
+
+
+def query(name, *args, out=(ctypes.c_size_t,)):
+    """Call an entry point whose trailing parameters are outputs of the ctypes types `out` (default: the one size_t of the
+    `*_bytes` queries); returns their values, a single one bare."""
+    outs = [t() for t in out]
+    call(name, *args, *[ctypes.byref(o) for o in outs])
+    return outs[0].value if len(outs) == 1 else tuple(o.value for o in outs)

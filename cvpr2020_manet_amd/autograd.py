@@ -43,15 +43,79 @@ import ctypes
 
 import torch
 
-from . import _lib
-
-
-def _stream_ptr(device):
-    return torch.cuda.current_stream(device).cuda_stream
+from . import _lib, ops
+from .ops import _bank_strides, _on, _optional, _ptr, _stream_ptr, _strided, _workspace, _ws_bytes
 
 
 def _scratch(device, nbytes):
     return torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
+
+
+def _dense(t):
+    """non-overlapping and dense (a permuted contiguous tensor): a new buffer can mirror its layout"""
+    if t.numel() == 0:
+        return False
+    sizes_strides = sorted(zip(t.stride(), t.shape))
+    expect = 1
+    for st, sz in sizes_strides:
+        if sz == 1:
+            continue
+        if st != expect:
+            return False
+        expect *= sz
+    return True
+
+
+def _grad_like(t, needed=True):
+    """a float32 gradient buffer in `t`'s own memory order (C-major embeddings stay C-major) if `t` is dense, contiguous
+    otherwise; None when the gradient is not `needed` (the frozen reference frame of fine-tuning: neither zero-filled nor
+    scattered into)"""
+    if not needed:
+        return None
+    if _dense(t):
+        return torch.empty_strided(t.shape, t.stride(), dtype=torch.float32, device=t.device)
+    return torch.empty(t.shape, dtype=torch.float32, device=t.device)
+
+
+def _global_arg_forward(bytes_query, symbol, ref, qry, labels, n_ids, ranks=()):
+    """the arg-min forward kernels -> (distances, winning bank rows), each [*ranks, N, n_ids]"""
+    M0, C = ref.shape
+    N = qry.shape[0]
+    dev = qry.device
+    ws = _scratch(dev, _lib.query(bytes_query, N, M0, C, n_ids))
+    d = torch.empty((*ranks, N, n_ids), dtype=torch.float32, device=dev)
+    arg = torch.empty((*ranks, N, n_ids), dtype=torch.int32, device=dev)
+    with _on(dev):
+        _lib.call(symbol, *_strided(qry), ref.data_ptr(), *_bank_strides(ref), labels.data_ptr(), N, M0, C, n_ids, *ranks,
+                  d.data_ptr(), arg.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    return d, arg
+
+
+def _global_backward_call(ref, qry, arg, g, n_ids, gq, gr, ranks=None):
+    """the gather / scatter-add of `g` through the recorded rows `arg` into gq / gr (None: not wanted).  ranks None: the atomic
+    route, one rank (manet_global_match_backward_f32); else arg / g are [ranks, N, n_ids] and the route is the ordered one."""
+    M0, C = ref.shape
+    N = qry.shape[0]
+    dev = qry.device
+    operands = (*_strided(qry), ref.data_ptr(), *_bank_strides(ref), arg.data_ptr(), g.data_ptr(), N, M0, C, n_ids)
+    grads = _optional(gq, C, 1) + (_optional(gr, C, 1) if M0 > 0 else (_ptr(gr), C, 1))
+    with _on(dev):
+        if ranks is None:
+            _lib.call("manet_global_match_backward_f32", *operands, *grads, _stream_ptr(dev))
+        else:
+            ws = _workspace(dev, "global_backward_ordered",
+                            _ws_bytes("manet_global_match_backward_ordered_workspace_bytes", N, M0, C, n_ids, ranks))
+            _lib.call("manet_global_match_backward_ordered_f32", *operands, ranks, *grads, ws.data_ptr(), ws.numel(),
+                      _stream_ptr(dev))
+
+
+def _global_backward(ctx, arg, g, ranks):
+    """_global_backward_call into gradients laid out like the inputs -> (grad_ref, grad_qry), None where not needed"""
+    ref, qry = ctx.saved_tensors[:2]
+    gr, gq = _grad_like(ref, ctx.needs_input_grad[0]), _grad_like(qry, ctx.needs_input_grad[1])
+    if gr is not None or gq is not None:
+        _global_backward_call(ref, qry, arg, g, ctx.n_ids, gq, gr, ranks)
+    return gr, gq
 
 
 class GlobalMatchFn(torch.autograd.Function):
@@ -59,22 +123,8 @@ class GlobalMatchFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ref, qry, labels, n_ids):
-        lib = _lib.load()
-        M0, C = ref.shape
-        N = qry.shape[0]
-        dev = qry.device
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.manet_global_match_arg_workspace_bytes(N, M0, C, n_ids, ctypes.byref(nbytes)),
-                   "manet_global_match_arg_workspace_bytes")
-        ws = _scratch(dev, nbytes.value)
-        out = torch.empty((N, n_ids), dtype=torch.float32, device=dev)
-        arg = torch.empty((N, n_ids), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.manet_global_match_arg_f32(qry.data_ptr(), qry.stride(0), qry.stride(1), ref.data_ptr(),
-                                                ref.stride(0) if M0 > 0 else C, ref.stride(1) if M0 > 0 else 1,
-                                                labels.data_ptr(), N, M0, C, n_ids, out.data_ptr(), arg.data_ptr(),
-                                                ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "manet_global_match_arg_f32")
+        out, arg = _global_arg_forward("manet_global_match_arg_workspace_bytes", "manet_global_match_arg_f32", ref, qry, labels,
+                                       n_ids)
         ctx.save_for_backward(ref, qry, arg)
         ctx.n_ids = n_ids
         ctx.mark_non_differentiable(arg)
@@ -82,35 +132,7 @@ class GlobalMatchFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out, _grad_arg):
-        lib = _lib.load()
-        ref, qry, arg = ctx.saved_tensors
-        M0, C = ref.shape
-        N = qry.shape[0]
-        dev = qry.device
-        g = grad_out.contiguous().float()
-        need_ref, need_qry = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_ref or need_qry):
-            return None, None, None, None
-        # gradients in the inputs' own memory order (C-major embeddings stay C-major); a gradient nobody asked for (the
-        # frozen reference frame of fine-tuning) is neither zero-filled nor scattered into
-        gq = gr = None
-        if need_qry:
-            gq = torch.empty_strided(qry.shape, qry.stride(), dtype=torch.float32, device=dev) \
-                if _dense(qry) else torch.empty(qry.shape, dtype=torch.float32, device=dev)
-        if need_ref:
-            gr = torch.empty_strided(ref.shape, ref.stride(), dtype=torch.float32, device=dev) \
-                if _dense(ref) else torch.empty(ref.shape, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.manet_global_match_backward_f32(qry.data_ptr(), qry.stride(0), qry.stride(1), ref.data_ptr(),
-                                                     ref.stride(0) if M0 > 0 else C, ref.stride(1) if M0 > 0 else 1,
-                                                     arg.data_ptr(), g.data_ptr(), N, M0, C, ctx.n_ids,
-                                                     None if gq is None else gq.data_ptr(),
-                                                     C if gq is None else gq.stride(0), 1 if gq is None else gq.stride(1),
-                                                     None if gr is None else gr.data_ptr(),
-                                                     C if (gr is None or M0 == 0) else gr.stride(0),
-                                                     1 if (gr is None or M0 == 0) else gr.stride(1), _stream_ptr(dev))
-        _lib.check(rc, "manet_global_match_backward_f32")
-        return gr, gq, None, None
+        return (*_global_backward(ctx, ctx.saved_tensors[2], grad_out.contiguous().float(), None), None, None)
 
 
 class GlobalMatchTopkFn(torch.autograd.Function):
@@ -123,22 +145,8 @@ class GlobalMatchTopkFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ref, qry, labels, n_ids, k):
-        lib = _lib.load()
-        M0, C = ref.shape
-        N = qry.shape[0]
-        dev = qry.device
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.manet_global_match_topk_arg_workspace_bytes(N, M0, C, n_ids, ctypes.byref(nbytes)),
-                   "manet_global_match_topk_arg_workspace_bytes")
-        ws = _scratch(dev, nbytes.value)
-        d = torch.empty((k, N, n_ids), dtype=torch.float32, device=dev)
-        arg = torch.empty((k, N, n_ids), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.manet_global_match_topk_arg_f32(qry.data_ptr(), qry.stride(0), qry.stride(1), ref.data_ptr(),
-                                                     ref.stride(0) if M0 > 0 else C, ref.stride(1) if M0 > 0 else 1,
-                                                     labels.data_ptr(), N, M0, C, n_ids, k, d.data_ptr(), arg.data_ptr(),
-                                                     ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "manet_global_match_topk_arg_f32")
+        d, arg = _global_arg_forward("manet_global_match_topk_arg_workspace_bytes", "manet_global_match_topk_arg_f32", ref, qry,
+                                     labels, n_ids, (k,))
         # IntVOS.py:88-94 on the k sorted distances (rank along dim 0)
         valid = d < 1e20
         masked = d * valid.float()
@@ -157,62 +165,22 @@ class GlobalMatchTopkFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         ref, qry, arg, wgt = ctx.saved_tensors
-        M0, C = ref.shape
-        N = qry.shape[0]
-        dev = qry.device
         need_ref, need_qry = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_ref or need_qry):
             return None, None, None, None, None
         g = grad_out.contiguous().float()
         gq_sum = gr_sum = None
-        for j in range(ctx.k):
+        for j in range(ctx.k):  # contiguous per-rank gradients, summed with torch
             gj = (g * wgt[j]).contiguous()
-            gq = torch.empty((N, C), dtype=torch.float32, device=dev) if need_qry else None
-            gr = torch.empty((M0, C), dtype=torch.float32, device=dev) if need_ref else None
-            with torch.cuda.device(dev):
-                rc = lib.manet_global_match_backward_f32(qry.data_ptr(), qry.stride(0), qry.stride(1), ref.data_ptr(),
-                                                         ref.stride(0) if M0 > 0 else C, ref.stride(1) if M0 > 0 else 1,
-                                                         arg[j].data_ptr(), gj.data_ptr(), N, M0, C, ctx.n_ids,
-                                                         None if gq is None else gq.data_ptr(), C, 1,
-                                                         None if gr is None else gr.data_ptr(), C, 1, _stream_ptr(dev))
-            _lib.check(rc, "manet_global_match_backward_f32")
+            gq = torch.empty(qry.shape, dtype=torch.float32, device=qry.device) if need_qry else None
+            gr = torch.empty(ref.shape, dtype=torch.float32, device=qry.device) if need_ref else None
+            _global_backward_call(ref, qry, arg[j], gj, ctx.n_ids, gq, gr)
             if need_qry:
                 gq_sum = gq if gq_sum is None else gq_sum.add_(gq)
             if need_ref:
                 gr_sum = gr if gr_sum is None else gr_sum.add_(gr)
         return gr_sum, gq_sum, None, None, None
-
-
-def _global_backward_ordered(ref, qry, arg, gw, n_ids, ranks, need_ref, need_qry):
-    """manet_global_match_backward_ordered_f32 on arg / gw [ranks, N, n_ids]: gradients in the inputs' own memory order"""
-    from . import ops
-    lib = _lib.load()
-    M0, C = ref.shape
-    N = qry.shape[0]
-    dev = qry.device
-    gq = gr = None
-    if need_qry:
-        gq = torch.empty_strided(qry.shape, qry.stride(), dtype=torch.float32, device=dev) \
-            if _dense(qry) else torch.empty(qry.shape, dtype=torch.float32, device=dev)
-    if need_ref:
-        gr = torch.empty_strided(ref.shape, ref.stride(), dtype=torch.float32, device=dev) \
-            if _dense(ref) else torch.empty(ref.shape, dtype=torch.float32, device=dev)
-    with ops._on(dev):
-        nbytes = ops._ws_bytes("manet_global_match_backward_ordered_workspace_bytes", N, M0, C, n_ids, ranks)
-        ws = ops._workspace(dev, "global_backward_ordered", nbytes)
-        rc = lib.manet_global_match_backward_ordered_f32(qry.data_ptr(), qry.stride(0), qry.stride(1), ref.data_ptr(),
-                                                         ref.stride(0) if M0 > 0 else C, ref.stride(1) if M0 > 0 else 1,
-                                                         arg.data_ptr(), gw.data_ptr(), N, M0, C, n_ids, ranks,
-                                                         None if gq is None else gq.data_ptr(),
-                                                         C if gq is None else gq.stride(0), 1 if gq is None else gq.stride(1),
-                                                         None if gr is None else gr.data_ptr(),
-                                                         C if (gr is None or M0 == 0) else gr.stride(0),
-                                                         1 if (gr is None or M0 == 0) else gr.stride(1), ws.data_ptr(), ws.numel(),
-                                                         _stream_ptr(dev))
-    _lib.check(rc, "manet_global_match_backward_ordered_f32")
-    return gr, gq
 
 
 class GlobalMatchOrderedFn(GlobalMatchFn):
@@ -221,13 +189,7 @@ class GlobalMatchOrderedFn(GlobalMatchFn):
 
     @staticmethod
     def backward(ctx, grad_out, _grad_arg):
-        ref, qry, arg = ctx.saved_tensors
-        need_ref, need_qry = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_ref or need_qry):
-            return None, None, None, None
-        g = grad_out.contiguous().float()
-        gr, gq = _global_backward_ordered(ref, qry, arg, g, ctx.n_ids, 1, need_ref, need_qry)
-        return gr, gq, None, None
+        return (*_global_backward(ctx, ctx.saved_tensors[2], grad_out.contiguous().float(), 1), None, None)
 
 
 class GlobalMatchTopkOrderedFn(GlobalMatchTopkFn):
@@ -236,28 +198,56 @@ class GlobalMatchTopkOrderedFn(GlobalMatchTopkFn):
 
     @staticmethod
     def backward(ctx, grad_out):
-        ref, qry, arg, wgt = ctx.saved_tensors
-        need_ref, need_qry = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_ref or need_qry):
+        arg, wgt = ctx.saved_tensors[2:]
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             return None, None, None, None, None
         gw = (grad_out.float().unsqueeze(0) * wgt).contiguous()
-        gr, gq = _global_backward_ordered(ref, qry, arg.contiguous(), gw, ctx.n_ids, ctx.k, need_ref, need_qry)
-        return gr, gq, None, None, None
+        return (*_global_backward(ctx, arg.contiguous(), gw, ctx.k), None, None, None)
 
 
-def _dense(t):
-    """non-overlapping and dense (a permuted contiguous tensor): empty_strided can mirror its layout"""
-    if t.numel() == 0:
-        return False
-    sizes_strides = sorted(zip(t.stride(), t.shape))
-    expect = 1
-    for st, sz in sizes_strides:
-        if sz == 1:
-            continue
-        if st != expect:
-            return False
-        expect *= sz
-    return True
+def _local_forward(ctx, ordered, prev, cur, labels, n_ids, max_distance):
+    """LocalMatchFn / LocalMatchOrderedFn.forward: the same out / arg / volume bits from either symbol; the atomic route sizes a
+    fresh scratch tensor per call, the ordered one uses the workspace cache"""
+    h, w, C = cur.shape
+    dev = cur.device
+    P = 2 * max_distance + 1
+    out = torch.empty((h, w, n_ids), dtype=torch.float32, device=dev)
+    arg = torch.empty((h, w, n_ids), dtype=torch.int32, device=dev)
+    vol = torch.empty((P * P, h // 2, w // 2), dtype=torch.float32, device=dev)
+    with _on(dev):
+        if ordered:
+            ws = _workspace(dev, "local_train", _ws_bytes("manet_local_match_arg_workspace_bytes", h, w, C, max_distance))
+        else:
+            ws = _scratch(dev, _lib.query("manet_local_match_arg_workspace_bytes", h, w, C, max_distance))
+        _lib.call("manet_local_match_train_forward_f32" if ordered else "manet_local_match_arg_f32", *_strided(prev),
+                  *_strided(cur), labels.data_ptr(), h, w, C, n_ids, max_distance, out.data_ptr(), arg.data_ptr(), vol.data_ptr(),
+                  ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    ctx.save_for_backward(prev, cur, vol, arg)
+    ctx.n_ids, ctx.max_distance = n_ids, max_distance
+    return out
+
+
+def _local_backward(ctx, ordered, grad_out):
+    """LocalMatchFn / LocalMatchOrderedFn.backward.  The atomic route computes both gradients, wanted or not; on the ordered one
+    a frozen frame gets None (a null pointer with zero strides) and no work."""
+    prev, cur, vol, arg = ctx.saved_tensors
+    need_prev, need_cur = ctx.needs_input_grad[:2] if ordered else (True, True)
+    if not (need_prev or need_cur):
+        return None, None, None, None, None
+    h, w, C = cur.shape
+    dev = cur.device
+    g = grad_out.contiguous().float()
+    gp, gc = _grad_like(prev, need_prev), _grad_like(cur, need_cur)
+    with _on(dev):
+        if ordered:
+            ws = _workspace(dev, "local_train_backward",
+                            _ws_bytes("manet_local_match_train_workspace_bytes", h, w, C, ctx.n_ids, ctx.max_distance))
+        else:
+            ws = _scratch(dev, _lib.query("manet_local_match_backward_workspace_bytes", h, w, C, ctx.max_distance))
+        _lib.call("manet_local_match_train_backward_f32" if ordered else "manet_local_match_backward_f32", *_strided(prev),
+                  *_strided(cur), vol.data_ptr(), arg.data_ptr(), g.data_ptr(), h, w, C, ctx.n_ids, ctx.max_distance,
+                  *_optional(gp, 0, 0, 0), *_optional(gc, 0, 0, 0), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    return gp, gc, None, None, None
 
 
 class LocalMatchFn(torch.autograd.Function):
@@ -265,52 +255,46 @@ class LocalMatchFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, prev, cur, labels, n_ids, max_distance):
-        lib = _lib.load()
-        h, w, C = cur.shape
-        dev = cur.device
-        P = 2 * max_distance + 1
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.manet_local_match_arg_workspace_bytes(h, w, C, max_distance, ctypes.byref(nbytes)),
-                   "manet_local_match_arg_workspace_bytes")
-        ws = _scratch(dev, nbytes.value)
-        out = torch.empty((h, w, n_ids), dtype=torch.float32, device=dev)
-        arg = torch.empty((h, w, n_ids), dtype=torch.int32, device=dev)
-        vol = torch.empty((P * P, h // 2, w // 2), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.manet_local_match_arg_f32(prev.data_ptr(), prev.stride(0), prev.stride(1), prev.stride(2),
-                                               cur.data_ptr(), cur.stride(0), cur.stride(1), cur.stride(2),
-                                               labels.data_ptr(), h, w, C, n_ids, max_distance, out.data_ptr(),
-                                               arg.data_ptr(), vol.data_ptr(), ws.data_ptr(), ws.numel(),
-                                               _stream_ptr(dev))
-        _lib.check(rc, "manet_local_match_arg_f32")
-        ctx.save_for_backward(prev, cur, vol, arg)
-        ctx.n_ids, ctx.max_distance = n_ids, max_distance
-        return out
+        return _local_forward(ctx, False, prev, cur, labels, n_ids, max_distance)
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
-        prev, cur, vol, arg = ctx.saved_tensors
-        h, w, C = cur.shape
-        dev = cur.device
-        g = grad_out.contiguous().float()
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.manet_local_match_backward_workspace_bytes(h, w, C, ctx.max_distance, ctypes.byref(nbytes)),
-                   "manet_local_match_backward_workspace_bytes")
-        ws = _scratch(dev, nbytes.value)
-        gp = torch.empty_strided(prev.shape, prev.stride(), dtype=torch.float32, device=dev) \
-            if _dense(prev) else torch.empty(prev.shape, dtype=torch.float32, device=dev)
-        gc = torch.empty_strided(cur.shape, cur.stride(), dtype=torch.float32, device=dev) \
-            if _dense(cur) else torch.empty(cur.shape, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.manet_local_match_backward_f32(prev.data_ptr(), prev.stride(0), prev.stride(1), prev.stride(2),
-                                                    cur.data_ptr(), cur.stride(0), cur.stride(1), cur.stride(2),
-                                                    vol.data_ptr(), arg.data_ptr(), g.data_ptr(), h, w, C, ctx.n_ids,
-                                                    ctx.max_distance, gp.data_ptr(), gp.stride(0), gp.stride(1),
-                                                    gp.stride(2), gc.data_ptr(), gc.stride(0), gc.stride(1),
-                                                    gc.stride(2), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "manet_local_match_backward_f32")
-        return gp, gc, None, None, None
+        return _local_backward(ctx, False, grad_out)
+
+
+class LocalMatchOrderedFn(LocalMatchFn):
+    """LocalMatchFn's ordered route: forward manet_local_match_train_forward_f32 (the same out / arg / volume bits, the masked
+    minimum spread over (2d+1) x 2 threads per pixel), backward manet_local_match_train_backward_f32 -- sparse, no float atomics,
+    every pooled cell's gradient added by one owner in an order fixed by indices; a frozen frame gets None and no work."""
+
+    @staticmethod
+    def forward(ctx, prev, cur, labels, n_ids, max_distance):
+        return _local_forward(ctx, True, prev, cur, labels, n_ids, max_distance)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return _local_backward(ctx, True, grad_out)
+
+
+def _local_full_backward(ctx, ordered, grad_out):
+    """LocalMatchFullFn / LocalMatchFullOrderedFn.backward; as in _local_backward, only the ordered route skips a frozen frame"""
+    prev, cur, arg = ctx.saved_tensors
+    need_prev, need_cur = ctx.needs_input_grad[:2] if ordered else (True, True)
+    if not (need_prev or need_cur):
+        return None, None, None, None, None
+    h, w, C = cur.shape
+    dev = cur.device
+    P = 2 * ctx.max_distance + 1
+    g = grad_out.contiguous().float()
+    pc, cc = prev.permute(2, 0, 1).contiguous(), cur.permute(2, 0, 1).contiguous()  # (no copy for C-major embeddings)
+    gp = torch.empty_like(pc) if need_prev else None
+    gc = torch.empty_like(cc) if need_cur else None
+    dv = torch.empty((P * P, h * w), dtype=torch.float32, device=dev)
+    with _on(dev):
+        _lib.call("manet_local_match_full_backward_ordered_f32" if ordered else "manet_local_match_full_backward_f32",
+                  pc.data_ptr(), cc.data_ptr(), arg.data_ptr(), g.data_ptr(), h, w, C, ctx.n_ids, ctx.max_distance, _ptr(gp),
+                  _ptr(gc), dv.data_ptr(), _stream_ptr(dev))
+    return (None if gp is None else gp.permute(1, 2, 0)), (None if gc is None else gc.permute(1, 2, 0)), None, None, None
 
 
 class LocalMatchFullFn(torch.autograd.Function):
@@ -320,101 +304,22 @@ class LocalMatchFullFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, prev, cur, labels, n_ids, max_distance):
-        lib = _lib.load()
         h, w, C = cur.shape
         dev = cur.device
         P = 2 * max_distance + 1
         out = torch.empty((h, w, n_ids), dtype=torch.float32, device=dev)
         arg = torch.empty((h, w, n_ids), dtype=torch.int32, device=dev)
         vol = torch.empty((h, w, P * P), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.manet_local_match_full_arg_f32(prev.data_ptr(), prev.stride(0), prev.stride(1), prev.stride(2),
-                                                    cur.data_ptr(), cur.stride(0), cur.stride(1), cur.stride(2),
-                                                    labels.data_ptr(), h, w, C, n_ids, max_distance, out.data_ptr(),
-                                                    arg.data_ptr(), vol.data_ptr(), _stream_ptr(dev))
-        _lib.check(rc, "manet_local_match_full_arg_f32")
+        with _on(dev):
+            _lib.call("manet_local_match_full_arg_f32", *_strided(prev), *_strided(cur), labels.data_ptr(), h, w, C, n_ids,
+                      max_distance, out.data_ptr(), arg.data_ptr(), vol.data_ptr(), _stream_ptr(dev))
         ctx.save_for_backward(prev, cur, arg)
         ctx.n_ids, ctx.max_distance = n_ids, max_distance
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
-        prev, cur, arg = ctx.saved_tensors
-        h, w, C = cur.shape
-        dev = cur.device
-        P = 2 * ctx.max_distance + 1
-        g = grad_out.contiguous().float()
-        pc, cc = prev.permute(2, 0, 1).contiguous(), cur.permute(2, 0, 1).contiguous()  # (no copy for C-major embeddings)
-        gp, gc = torch.empty_like(pc), torch.empty_like(cc)
-        dv = torch.empty((P * P, h * w), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.manet_local_match_full_backward_f32(pc.data_ptr(), cc.data_ptr(), arg.data_ptr(), g.data_ptr(), h, w, C,
-                                                         ctx.n_ids, ctx.max_distance, gp.data_ptr(), gc.data_ptr(),
-                                                         dv.data_ptr(), _stream_ptr(dev))
-        _lib.check(rc, "manet_local_match_full_backward_f32")
-        return gp.permute(1, 2, 0), gc.permute(1, 2, 0), None, None, None
-
-
-class LocalMatchOrderedFn(torch.autograd.Function):
-    """LocalMatchFn's ordered route: forward manet_local_match_train_forward_f32 (the same out / arg / volume bits, the masked
-    minimum spread over (2d+1) x 2 threads per pixel), backward manet_local_match_train_backward_f32 -- sparse, no float atomics,
-    every pooled cell's gradient added by one owner in an order fixed by indices; a frozen frame gets None and no work."""
-
-    @staticmethod
-    def forward(ctx, prev, cur, labels, n_ids, max_distance):
-        from . import ops
-        lib = _lib.load()
-        h, w, C = cur.shape
-        dev = cur.device
-        P = 2 * max_distance + 1
-        out = torch.empty((h, w, n_ids), dtype=torch.float32, device=dev)
-        arg = torch.empty((h, w, n_ids), dtype=torch.int32, device=dev)
-        vol = torch.empty((P * P, h // 2, w // 2), dtype=torch.float32, device=dev)
-        with ops._on(dev):
-            nbytes = ops._ws_bytes("manet_local_match_arg_workspace_bytes", h, w, C, max_distance)
-            ws = ops._workspace(dev, "local_train", nbytes)
-            rc = lib.manet_local_match_train_forward_f32(prev.data_ptr(), prev.stride(0), prev.stride(1), prev.stride(2),
-                                                         cur.data_ptr(), cur.stride(0), cur.stride(1), cur.stride(2),
-                                                         labels.data_ptr(), h, w, C, n_ids, max_distance, out.data_ptr(),
-                                                         arg.data_ptr(), vol.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                         _stream_ptr(dev))
-        _lib.check(rc, "manet_local_match_train_forward_f32")
-        ctx.save_for_backward(prev, cur, vol, arg)
-        ctx.n_ids, ctx.max_distance = n_ids, max_distance
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        from . import ops
-        lib = _lib.load()
-        prev, cur, vol, arg = ctx.saved_tensors
-        need_prev, need_cur = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_prev or need_cur):
-            return None, None, None, None, None
-        h, w, C = cur.shape
-        dev = cur.device
-        g = grad_out.contiguous().float()
-        gp = gc = None
-        if need_prev:
-            gp = torch.empty_strided(prev.shape, prev.stride(), dtype=torch.float32, device=dev) \
-                if _dense(prev) else torch.empty(prev.shape, dtype=torch.float32, device=dev)
-        if need_cur:
-            gc = torch.empty_strided(cur.shape, cur.stride(), dtype=torch.float32, device=dev) \
-                if _dense(cur) else torch.empty(cur.shape, dtype=torch.float32, device=dev)
-        with ops._on(dev):
-            nbytes = ops._ws_bytes("manet_local_match_train_workspace_bytes", h, w, C, ctx.n_ids, ctx.max_distance)
-            ws = ops._workspace(dev, "local_train_backward", nbytes)
-            rc = lib.manet_local_match_train_backward_f32(prev.data_ptr(), prev.stride(0), prev.stride(1), prev.stride(2),
-                                                          cur.data_ptr(), cur.stride(0), cur.stride(1), cur.stride(2),
-                                                          vol.data_ptr(), arg.data_ptr(), g.data_ptr(), h, w, C, ctx.n_ids,
-                                                          ctx.max_distance, None if gp is None else gp.data_ptr(),
-                                                          *((0, 0, 0) if gp is None else gp.stride()),
-                                                          None if gc is None else gc.data_ptr(),
-                                                          *((0, 0, 0) if gc is None else gc.stride()), ws.data_ptr(), ws.numel(),
-                                                          _stream_ptr(dev))
-        _lib.check(rc, "manet_local_match_train_backward_f32")
-        return gp, gc, None, None, None
+        return _local_full_backward(ctx, False, grad_out)
 
 
 class LocalMatchFullOrderedFn(LocalMatchFullFn):
@@ -423,27 +328,7 @@ class LocalMatchFullOrderedFn(LocalMatchFullFn):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
-        prev, cur, arg = ctx.saved_tensors
-        need_prev, need_cur = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_prev or need_cur):
-            return None, None, None, None, None
-        h, w, C = cur.shape
-        dev = cur.device
-        P = 2 * ctx.max_distance + 1
-        g = grad_out.contiguous().float()
-        pc, cc = prev.permute(2, 0, 1).contiguous(), cur.permute(2, 0, 1).contiguous()  # (no copy for C-major embeddings)
-        gp = torch.empty_like(pc) if need_prev else None
-        gc = torch.empty_like(cc) if need_cur else None
-        dv = torch.empty((P * P, h * w), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = lib.manet_local_match_full_backward_ordered_f32(pc.data_ptr(), cc.data_ptr(), arg.data_ptr(), g.data_ptr(), h, w,
-                                                                 C, ctx.n_ids, ctx.max_distance,
-                                                                 None if gp is None else gp.data_ptr(),
-                                                                 None if gc is None else gc.data_ptr(), dv.data_ptr(),
-                                                                 _stream_ptr(dev))
-        _lib.check(rc, "manet_local_match_full_backward_ordered_f32")
-        return (None if gp is None else gp.permute(1, 2, 0)), (None if gc is None else gc.permute(1, 2, 0)), None, None, None
+        return _local_full_backward(ctx, True, grad_out)
 
 
 class CorrelationFn(torch.autograd.Function):
@@ -454,7 +339,6 @@ class CorrelationFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2):
-        from . import ops
         if input1.dtype != input2.dtype:
             raise RuntimeError("cvpr2020_manet_amd: correlation inputs must have the same dtype")
         a = input1.contiguous()
@@ -466,7 +350,6 @@ class CorrelationFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         a0, b0 = ctx.saved_tensors
         wide = torch.float64 if a0.dtype == torch.float64 else torch.float32
         a, b = a0.to(wide), b0.to(wide)
@@ -474,11 +357,10 @@ class CorrelationFn(torch.autograd.Function):
         pad_size, kernel_size, max_displacement, stride1, stride2 = ctx.params
         g = grad_out.contiguous().to(wide)
         ga, gb = torch.empty_like(a), torch.empty_like(b)
-        fn = lib.manet_correlation_backward_f64 if wide == torch.float64 else lib.manet_correlation_backward_f32
-        with torch.cuda.device(a.device):
-            rc = fn(a.data_ptr(), b.data_ptr(), g.data_ptr(), B, C, H, W, pad_size, kernel_size, max_displacement, stride1,
-                    stride2, ga.data_ptr(), gb.data_ptr(), _stream_ptr(a.device))
-        _lib.check(rc, "manet_correlation_backward")
+        with _on(a.device):
+            _lib.call("manet_correlation_backward_f64" if wide == torch.float64 else "manet_correlation_backward_f32", a.data_ptr(),
+                      b.data_ptr(), g.data_ptr(), B, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2,
+                      ga.data_ptr(), gb.data_ptr(), _stream_ptr(a.device))
         return ga.to(a0.dtype), gb.to(b0.dtype), None, None, None, None, None
 
 
@@ -490,7 +372,6 @@ class DepthwiseConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        from . import ops
         x = x.contiguous()
         wt = weight.contiguous()
         with torch.no_grad():
@@ -501,7 +382,6 @@ class DepthwiseConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         x, wt = ctx.saved_tensors
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
         B, C, h, w = x.shape
@@ -509,22 +389,17 @@ class DepthwiseConvFn(torch.autograd.Function):
         dev = x.device
         g = grad_out.contiguous().float()
         gx = gw = gb = None
-        with torch.cuda.device(dev):
+        with _on(dev):
             if need_x:
                 gx = torch.empty_like(x)
-                _lib.check(lib.manet_dwconv_backward_data_f32(g.data_ptr(), B, C, h, w, K, wt.data_ptr(), gx.data_ptr(),
-                                                              _stream_ptr(dev)), "manet_dwconv_backward_data_f32")
+                _lib.call("manet_dwconv_backward_data_f32", g.data_ptr(), B, C, h, w, K, wt.data_ptr(), gx.data_ptr(),
+                          _stream_ptr(dev))
             if need_w or need_b:
-                nbytes = ctypes.c_size_t(0)
-                _lib.check(lib.manet_dwconv_backward_weight_workspace_bytes(B, C, h, w, K, ctypes.byref(nbytes)),
-                           "manet_dwconv_backward_weight_workspace_bytes")
-                ws = _scratch(dev, nbytes.value)
+                ws = _scratch(dev, _lib.query("manet_dwconv_backward_weight_workspace_bytes", B, C, h, w, K))
                 gw_full = torch.empty_like(wt)
                 gb_full = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
-                _lib.check(lib.manet_dwconv_backward_weight_f32(x.data_ptr(), g.data_ptr(), B, C, h, w, K, gw_full.data_ptr(),
-                                                                None if gb_full is None else gb_full.data_ptr(), ws.data_ptr(),
-                                                                ws.numel(), _stream_ptr(dev)),
-                           "manet_dwconv_backward_weight_f32")
+                _lib.call("manet_dwconv_backward_weight_f32", x.data_ptr(), g.data_ptr(), B, C, h, w, K, gw_full.data_ptr(),
+                          _ptr(gb_full), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
                 gw = gw_full if need_w else None
                 gb = gb_full
         return gx, gw, gb
@@ -538,7 +413,6 @@ class PointwiseConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        from . import ops
         x = x.contiguous()
         wt = weight.detach().reshape(weight.shape[0], weight.shape[1]).contiguous()
         with torch.no_grad():
@@ -550,30 +424,25 @@ class PointwiseConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         x, wt = ctx.saved_tensors
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
-        from . import ops
         B, Cin, h, w = x.shape
         Cout = wt.shape[0]
         dev = x.device
         g = grad_out.contiguous().float()
         gx = gw = gb = None
-        with ops._on(dev):
+        with _on(dev):
             st = _stream_ptr(dev)
             if need_x:
                 gx = torch.empty_like(x)
-                _lib.check(lib.manet_pw_backward_data_f32(g.data_ptr(), B, Cin, Cout, h * w, wt.data_ptr(), gx.data_ptr(), st),
-                           "manet_pw_backward_data_f32")
+                _lib.call("manet_pw_backward_data_f32", g.data_ptr(), B, Cin, Cout, h * w, wt.data_ptr(), gx.data_ptr(), st)
             if need_w or need_b:
-                nbytes = ops._ws_bytes("manet_pw_backward_weight_workspace_bytes", B, Cin, Cout, h * w)
-                ws = ops._workspace(dev, "pw_backward_weight", nbytes)
+                nbytes = _ws_bytes("manet_pw_backward_weight_workspace_bytes", B, Cin, Cout, h * w)
+                ws = _workspace(dev, "pw_backward_weight", nbytes)
                 gw = torch.empty(ctx.wshape, dtype=torch.float32, device=dev) if need_w else None
                 gb = torch.empty((Cout,), dtype=torch.float32, device=dev) if need_b else None
-                _lib.check(lib.manet_pw_backward_weight_f32(x.data_ptr(), g.data_ptr(), B, Cin, Cout, h * w,
-                                                            None if gw is None else gw.data_ptr(),
-                                                            None if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, st),
-                           "manet_pw_backward_weight_f32")
+                _lib.call("manet_pw_backward_weight_f32", x.data_ptr(), g.data_ptr(), B, Cin, Cout, h * w, _ptr(gw), _ptr(gb),
+                          ws.data_ptr(), nbytes, st)
         return gx, gw, gb
 
 
@@ -585,7 +454,6 @@ class BatchNormReluFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, training):
-        from . import ops
         x = x.contiguous()
         with torch.no_grad():
             out, save = ops._bn_relu_forward(x, weight, bias, running_mean, running_var, momentum, eps, training)
@@ -595,7 +463,6 @@ class BatchNormReluFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
         x, weight, bias, save = ctx.saved_tensors
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         B, C, h, w = x.shape
@@ -606,15 +473,12 @@ class BatchNormReluFn(torch.autograd.Function):
         gb = torch.empty((C,), dtype=torch.float32, device=dev) if need_b else None
         if gx is None and gw is None and gb is None:
             return None, None, None, None, None, None, None, None
-        from . import ops
-        with ops._on(dev):
-            nbytes = ops._ws_bytes("manet_bn_relu_workspace_bytes", B, C, h * w)
-            ws = ops._workspace(dev, "bn_relu", nbytes)
-            _lib.check(lib.manet_bn_relu_backward_f32(g.data_ptr(), x.data_ptr(), B, C, h * w, weight.data_ptr(), bias.data_ptr(),
-                                                      save.data_ptr(), save.data_ptr() + 4 * C, 1 if ctx.training else 0,
-                                                      None if gx is None else gx.data_ptr(), None if gw is None else gw.data_ptr(),
-                                                      None if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(dev)),
-                       "manet_bn_relu_backward_f32")
+        with _on(dev):
+            nbytes = _ws_bytes("manet_bn_relu_workspace_bytes", B, C, h * w)
+            ws = _workspace(dev, "bn_relu", nbytes)
+            _lib.call("manet_bn_relu_backward_f32", g.data_ptr(), x.data_ptr(), B, C, h * w, weight.data_ptr(), bias.data_ptr(),
+                      save.data_ptr(), save.data_ptr() + 4 * C, 1 if ctx.training else 0, _ptr(gx), _ptr(gw), _ptr(gb),
+                      ws.data_ptr(), nbytes, _stream_ptr(dev))
         return gx, gw, gb, None, None, None, None, None
 
 
@@ -625,7 +489,6 @@ class OutputConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        from . import ops
         x = x.contiguous()
         wt = weight.detach().contiguous()
         with torch.no_grad():
@@ -636,7 +499,6 @@ class OutputConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import ops
         x, wt = ctx.saved_tensors
         need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2] and ctx.has_bias
         if not (need_x or need_w or need_b):
@@ -647,24 +509,21 @@ class OutputConvFn(torch.autograd.Function):
         gx = torch.empty_like(x) if need_x else None
         gw = torch.empty_like(wt) if need_w else None
         gb = torch.empty((1,), dtype=torch.float32, device=dev) if need_b else None
-        with ops._on(dev):
-            nbytes = ops._ws_bytes("manet_out_conv_workspace_bytes", B, C, h * w)
-            ws = ops._workspace(dev, "out_conv", nbytes)
-            rc = _lib.load().manet_out_conv_backward_f32(g.data_ptr(), x.data_ptr(), B, C, h * w, wt.data_ptr(),
-                                                         None if gx is None else gx.data_ptr(), None if gw is None else gw.data_ptr(),
-                                                         None if gb is None else gb.data_ptr(), ws.data_ptr(), nbytes, _stream_ptr(dev))
-        _lib.check(rc, "manet_out_conv_backward_f32")
+        with _on(dev):
+            nbytes = _ws_bytes("manet_out_conv_workspace_bytes", B, C, h * w)
+            ws = _workspace(dev, "out_conv", nbytes)
+            _lib.call("manet_out_conv_backward_f32", g.data_ptr(), x.data_ptr(), B, C, h * w, wt.data_ptr(), _ptr(gx), _ptr(gw),
+                      _ptr(gb), ws.data_ptr(), nbytes, _stream_ptr(dev))
         return gx, gw, gb
 
 
 def _head_bytes(B, Cin, Cmid, h, w, K):
-    saved, ws = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    _lib.check(_lib.load().manet_head_train_bytes(B, Cin, Cmid, h, w, K, ctypes.byref(saved), ctypes.byref(ws)), "manet_head_train_bytes")
-    return saved.value, ws.value
+    """(bytes of the saved activations, bytes of the workspace) of one head's training step"""
+    return _lib.query("manet_head_train_bytes", B, Cin, Cmid, h, w, K, out=(ctypes.c_size_t,) * 2)
 
 
 def _ptr_array(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+    return (ctypes.c_void_p * len(tensors))(*[_ptr(t) for t in tensors])
 
 
 class DynamicSegHeadFn(torch.autograd.Function):
@@ -678,7 +537,6 @@ class DynamicSegHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, head, x, *params):
-        from . import ops
         x = x.contiguous()
         tensors = ops.dynamic_seghead_tensors(head)
         bns = ops.dynamic_seghead_bns(head)
@@ -691,12 +549,10 @@ class DynamicSegHeadFn(torch.autograd.Function):
         training = (ctypes.c_int * 8)(*[1 if bn.training else 0 for bn in bns])
         momentum = (ctypes.c_float * 8)(*[float(bn.momentum) for bn in bns])
         eps = (ctypes.c_float * 8)(*[float(bn.eps) for bn in bns])
-        with ops._on(dev):
-            ws = ops._workspace(dev, "head_train", ws_bytes)
-            rc = _lib.load().manet_head_train_forward_f32(x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(tensors), training, momentum, eps,
-                                                          saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, logits.data_ptr(),
-                                                          _stream_ptr(dev))
-        _lib.check(rc, "manet_head_train_forward_f32")
+        with _on(dev):
+            ws = _workspace(dev, "head_train", ws_bytes)
+            _lib.call("manet_head_train_forward_f32", x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(tensors), training, momentum,
+                      eps, saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, logits.data_ptr(), _stream_ptr(dev))
         # the backward reads parameters, not running statistics: those slots stay NULL there
         ctx.slots = [i for i, name in enumerate(ops.HEAD_BLOCK_TENSORS * 4 + ("conv.weight", "conv.bias")) if "running" not in name]
         ctx.present = [p is not None for p in params]
@@ -707,7 +563,6 @@ class DynamicSegHeadFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        from . import ops
         x, saved, *kept = ctx.saved_tensors
         B, Cin, Cmid, h, w, K = ctx.dims
         dev = x.device
@@ -723,12 +578,11 @@ class DynamicSegHeadFn(torch.autograd.Function):
         for slot, p, gp in zip(ctx.slots, params, grads):
             p50[slot], g50[slot] = p, gp
         saved_bytes, ws_bytes = _head_bytes(B, Cin, Cmid, h, w, K)
-        with ops._on(dev):
-            ws = ops._workspace(dev, "head_train", ws_bytes)
-            rc = _lib.load().manet_head_train_backward_f32(g.data_ptr(), x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(p50), ctx.training,
-                                                           saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, _ptr_array(g50),
-                                                           None if gx is None else gx.data_ptr(), _stream_ptr(dev))
-        _lib.check(rc, "manet_head_train_backward_f32")
+        with _on(dev):
+            ws = _workspace(dev, "head_train", ws_bytes)
+            _lib.call("manet_head_train_backward_f32", g.data_ptr(), x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(p50),
+                      ctx.training, saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, _ptr_array(g50), _ptr(gx),
+                      _stream_ptr(dev))
         return (None, gx) + tuple(grads)
 
 
@@ -741,7 +595,6 @@ class UpsampledCrossEntropyTopKFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels, size, k, divisor):
-        from . import ops
         logits = logits.detach()
         with torch.no_grad():
             loss, pix, stats = ops._loss_forward(logits, labels, size, k, divisor)
@@ -753,7 +606,6 @@ class UpsampledCrossEntropyTopKFn(torch.autograd.Function):
     def backward(ctx, grad_out):
         if not ctx.needs_input_grad[0]:
             return None, None, None, None, None
-        from . import ops
         logits, labels, pix, stats = ctx.saved_tensors
         dev = logits.device
         B = logits.shape[0]
@@ -761,9 +613,8 @@ class UpsampledCrossEntropyTopKFn(torch.autograd.Function):
         if g.dtype != torch.float32 or not g.is_contiguous():
             g = g.float().contiguous()
         gl = torch.empty(logits.shape, dtype=torch.float32, device=dev)
-        with ops._on(dev):
-            rc = _lib.load().manet_loss_ce_topk_backward_f32(*ops._loss_args(logits, labels, ctx.size), ctx.k, ctx.divisor,
-                                                             pix.data_ptr(), stats.data_ptr(), stats.data_ptr() + 4 * B,
-                                                             stats.data_ptr() + 8 * B, g.data_ptr(), gl.data_ptr(), _stream_ptr(dev))
-        _lib.check(rc, "manet_loss_ce_topk_backward_f32")
+        with _on(dev):
+            _lib.call("manet_loss_ce_topk_backward_f32", *ops._loss_args(logits, labels, ctx.size), ctx.k, ctx.divisor,
+                      pix.data_ptr(), stats.data_ptr(), stats.data_ptr() + 4 * B, stats.data_ptr() + 8 * B, g.data_ptr(),
+                      gl.data_ptr(), _stream_ptr(dev))
         return gl, None, None, None, None

@@ -60,17 +60,9 @@ def _global_match_autograd(reference_embeddings, query_embeddings, reference_lab
     if COMPUTE[compute] != _lib.COMPUTE_F32 or not 1 <= k_nearest_neighbors <= 8:
         raise RuntimeError("cvpr2020_manet_amd.ops.global_match: the backward exists for compute='f32' and "
                            "k_nearest_neighbors 1..8 only (got k=%d, compute=%r)" % (k_nearest_neighbors, compute))
-    ref, M0, C = _flat(reference_embeddings, "reference_embeddings")
-    qry, N, C2 = _flat(query_embeddings, "query_embeddings")
-    if C != C2:
-        raise ValueError("embedding_dim mismatch: %d vs %d" % (C, C2))
-    lab = _labels(reference_labels, "reference_labels")
-    if lab.numel() != M0:
-        raise ValueError("reference_labels has %d entries for %d reference pixels" % (lab.numel(), M0))
+    ref, qry, lab = _match_operands(reference_embeddings, query_embeddings, reference_labels, k_nearest_neighbors)
     ref, qry = ref.float(), qry.float()  # (a differentiable widening if the embeddings are stored in bf16)
     if k_nearest_neighbors > 1:
-        if M0 < k_nearest_neighbors:
-            raise RuntimeError("selected index k out of range")  # what torch.topk raises (IntVOS.py:87)
         out = GlobalMatchTopkFn.apply(ref, qry, lab, n_ids, int(k_nearest_neighbors))
     else:
         out, _ = GlobalMatchFn.apply(ref, qry, lab, n_ids)
@@ -100,8 +92,8 @@ _NO_SWITCH = _NoSwitch()
 
 
 def _on(device):
-    """`with _on(dev):` = `with _on(dev):`, minus the guard object when `dev` already is the current device (the
-    usual case: ~4 us of host time per call, 20 calls per propagated frame -- the eager loop is host-bound)"""
+    """`with _on(dev):` replaces `with torch.cuda.device(dev):`, minus the guard object when `dev` already is the current
+    device (the usual case: ~4 us of host time per call, 20 calls per propagated frame -- the eager loop is host-bound)"""
     return _NO_SWITCH if torch.cuda.current_device() == device.index else torch.cuda.device(device)
 
 
@@ -145,9 +137,54 @@ def _flat(t, name):
     return t2, t2.shape[0], t2.shape[1]
 
 
-def _labels(t, name):
+def _labels(t, name, count):
+    """flat contiguous int32 labels, one per pixel: `count` of them"""
     _need_gpu(t, name)
-    return t.reshape(-1).to(torch.int32).contiguous()
+    lab = t.reshape(-1).to(torch.int32).contiguous()
+    if lab.numel() != count:
+        raise ValueError("%s has %d entries for %d pixels" % (name, lab.numel(), count))
+    return lab
+
+
+def _match_operands(reference_embeddings, query_embeddings, reference_labels, k_nearest_neighbors):
+    """the global match's operands, flattened and validated -> (ref [M0, C], qry [N, C], int32 labels [M0])"""
+    ref, M0, C = _flat(reference_embeddings, "reference_embeddings")
+    qry, _, C2 = _flat(query_embeddings, "query_embeddings")
+    if C != C2:
+        raise ValueError("embedding_dim mismatch: %d vs %d" % (C, C2))
+    lab = _labels(reference_labels, "reference_labels", M0)
+    if k_nearest_neighbors > 1 and M0 < k_nearest_neighbors:
+        raise RuntimeError("selected index k out of range")  # what torch.topk raises (IntVOS.py:87)
+    return ref, qry, lab
+
+
+def _mem_ptr(mem, count):
+    """pointer of the optional stored map the epilogue merges into (None: null); `count` contiguous float32 on the GPU"""
+    if mem is None:
+        return None
+    _need_gpu(mem, "mem")
+    if mem.dtype != torch.float32 or not mem.is_contiguous() or mem.numel() != count:
+        raise ValueError("mem must be a contiguous float32 tensor of %d elements" % count)
+    return mem.data_ptr()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _strided(t):
+    """(pointer, *element strides): how the C ABI takes a tensor of any strides"""
+    return (t.data_ptr(), *t.stride())
+
+
+def _bank_strides(ref):
+    """element strides of a [M0, C] bank; an empty bank goes as (C, 1)"""
+    return ref.stride() if ref.shape[0] > 0 else (ref.shape[1], 1)
+
+
+def _optional(t, *placeholder):
+    """_strided(t) of an output that may not be wanted: None goes as a null pointer with the `placeholder` strides"""
+    return (None, *placeholder) if t is None else (t.data_ptr(), *t.stride())
 
 
 def global_match(reference_embeddings, query_embeddings, reference_labels, n_ids, k_nearest_neighbors=1,
@@ -159,41 +196,21 @@ def global_match(reference_embeddings, query_embeddings, reference_labels, n_ids
     deterministic=True: when the call is differentiated, the backward is the ordered, atomic-free one (the same gradient bits
     on every run); forward values are the same either way.
     """
-    import ctypes
     if _wants_grad(reference_embeddings, query_embeddings, mem):
         return _global_match_autograd(reference_embeddings, query_embeddings, reference_labels, n_ids,
                                       k_nearest_neighbors, compute, normalize, mem, deterministic)
-    lib = _lib.load()
-    ref, M0, C = _flat(reference_embeddings, "reference_embeddings")
-    qry, N, C2 = _flat(query_embeddings, "query_embeddings")
-    if C != C2:
-        raise ValueError("embedding_dim mismatch: %d vs %d" % (C, C2))
-    lab = _labels(reference_labels, "reference_labels")
-    if lab.numel() != M0:
-        raise ValueError("reference_labels has %d entries for %d reference pixels" % (lab.numel(), M0))
-    if k_nearest_neighbors > 1 and M0 < k_nearest_neighbors:
-        raise RuntimeError("selected index k out of range")  # what torch.topk raises (IntVOS.py:87)
+    ref, qry, lab = _match_operands(reference_embeddings, query_embeddings, reference_labels, k_nearest_neighbors)
+    (M0, C), N = ref.shape, qry.shape[0]
     dev = qry.device
     cmp_ = COMPUTE[compute]
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.manet_global_match_workspace_bytes(N, M0, C, n_ids, k_nearest_neighbors, cmp_,
-                                                      ctypes.byref(nbytes)), "manet_global_match_workspace_bytes")
-    ws = _workspace(dev, "global", nbytes.value)
+    ws = _workspace(dev, "global", _lib.query("manet_global_match_workspace_bytes", N, M0, C, n_ids, k_nearest_neighbors, cmp_))
     out = torch.empty((N, n_ids), dtype=torch.float32, device=dev)
-    mem_ptr = None
-    if mem is not None:
-        _need_gpu(mem, "mem")
-        if mem.dtype != torch.float32 or not mem.is_contiguous() or mem.numel() != N * n_ids:
-            raise ValueError("mem must be a contiguous float32 tensor of N*n_ids elements")
-        mem_ptr = mem.data_ptr()
+    mem_ptr = _mem_ptr(mem, N * n_ids)
     flags = _lib.EPI_NORMALIZE if normalize else 0
     with _on(dev):
-        rc = lib.manet_global_match_ex(qry.data_ptr(), _emb_code(qry), qry.stride(0), qry.stride(1), ref.data_ptr(),
-                                       _emb_code(ref), ref.stride(0) if M0 > 0 else C, ref.stride(1) if M0 > 0 else 1,
-                                       lab.data_ptr(), N, M0, C, n_ids, k_nearest_neighbors, cmp_,
-                                       out.data_ptr(), mem_ptr, flags, ws.data_ptr(), ws.numel(),
-                                       _stream_ptr(dev))
-    _lib.check(rc, "manet_global_match_ex")
+        _lib.call("manet_global_match_ex", qry.data_ptr(), _emb_code(qry), *qry.stride(), ref.data_ptr(), _emb_code(ref),
+                  *_bank_strides(ref), lab.data_ptr(), N, M0, C, n_ids, k_nearest_neighbors, cmp_, out.data_ptr(), mem_ptr,
+                  flags, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
     return out
 
 
@@ -218,31 +235,22 @@ class PreparedBank:
     def __init__(self, reference_embeddings, reference_labels, n_ids, compute="f32", reuse=None):
         """reuse: a PreparedBank that is no longer needed -- its workspace is taken over when it is large enough (a new
         interaction round re-prepares a bank of the same size: no 50-100 MB allocation per round)"""
-        import ctypes
         _refuse_autograd("PreparedBank", reference_embeddings)
-        lib = _lib.load()
         ref, M0, C = _flat(reference_embeddings, "reference_embeddings")
-        lab = _labels(reference_labels, "reference_labels")
-        if lab.numel() != M0:
-            raise ValueError("reference_labels has %d entries for %d reference pixels" % (lab.numel(), M0))
+        lab = _labels(reference_labels, "reference_labels", M0)
         self.M0, self.C, self.n_ids, self.compute = M0, C, n_ids, COMPUTE[compute]
         self.device = ref.device
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.manet_bank_workspace_bytes(M0, C, n_ids, self.compute, ctypes.byref(nbytes)),
-                   "manet_bank_workspace_bytes")
+        nbytes = _lib.query("manet_bank_workspace_bytes", M0, C, n_ids, self.compute)  # (reads a tuning knob: asked per bank)
         if getattr(reuse, "_adapt", None) is not None:
             self._adapt = reuse._adapt  # (what the previous bank of this clip learnt about its embeddings carries over)
         old = getattr(reuse, "ws", None)
-        if old is not None and old.device == self.device and old.numel() >= nbytes.value:
+        if old is not None and old.device == self.device and old.numel() >= nbytes:
             self.ws, reuse.ws = old, None
         else:
-            self.ws = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         with _on(self.device):
-            rc = lib.manet_bank_prepare_ex(ref.data_ptr(), _emb_code(ref), ref.stride(0) if M0 > 0 else C,
-                                           ref.stride(1) if M0 > 0 else 1, lab.data_ptr(), M0, C, n_ids,
-                                           self.compute, self.ws.data_ptr(), self.ws.numel(),
-                                           _stream_ptr(self.device))
-        _lib.check(rc, "manet_bank_prepare_ex")
+            _lib.call("manet_bank_prepare_ex", ref.data_ptr(), _emb_code(ref), *_bank_strides(ref), lab.data_ptr(), M0, C, n_ids,
+                      self.compute, self.ws.data_ptr(), self.ws.numel(), _stream_ptr(self.device))
 
     # compute="bf16r", adaptive policy: a frame whose filter pass sent more than this share of its query tiles to the rescue
     # pass (the exact fp32 kernel) cost the filter AND most of the fp32 kernel; the next ADAPT_FRAMES frames then skip the
@@ -257,8 +265,6 @@ class PreparedBank:
         adaptive (compute="bf16r" only): let the previous frames' rescue share decide whether this frame runs the bf16 filter at
         all (see ADAPT_SHARE); the result is the fp32 kernel's bit for bit either way.  The share arrives by an asynchronous copy
         and is read a frame late -- no synchronisation; nothing adapts inside a HIP-graph capture."""
-        import ctypes
-        lib = _lib.load()
         armed, raw = False, None
         if isinstance(query_embeddings, (PackedQuery, PreparedFrame)):
             pq = query_embeddings
@@ -281,19 +287,11 @@ class PreparedBank:
         if k_nearest_neighbors > 1 and self.M0 < k_nearest_neighbors:
             raise RuntimeError("selected index k out of range")
         dev = qry.device if isinstance(qry, torch.Tensor) else self.device
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.manet_match_workspace_bytes(N, self.M0, C, self.n_ids, k_nearest_neighbors,
-                                                   self.compute, ctypes.byref(nbytes)),
-                   "manet_match_workspace_bytes")
-        ws = _armed_workspace(dev, "match_armed", nbytes.value) if armed else _workspace(dev, "match", nbytes.value)
+        nbytes = _lib.query("manet_match_workspace_bytes", N, self.M0, C, self.n_ids, k_nearest_neighbors, self.compute)
+        ws = _armed_workspace(dev, "match_armed", nbytes) if armed else _workspace(dev, "match", nbytes)
         if out is None:
             out = torch.empty((N, self.n_ids), dtype=torch.float32, device=dev)
-        mem_ptr = None
-        if mem is not None:
-            _need_gpu(mem, "mem")
-            if mem.dtype != torch.float32 or not mem.is_contiguous() or mem.numel() != N * self.n_ids:
-                raise ValueError("mem must be a contiguous float32 tensor of N*n_ids elements")
-            mem_ptr = mem.data_ptr()
+        mem_ptr = _mem_ptr(mem, N * self.n_ids)
         flags = (_lib.EPI_NORMALIZE if normalize else 0) | (_lib.EPI_KEYS_ARMED if armed else 0)
         self._last = (ws, N)  # (refine_stats)
         refine = self.compute == _lib.COMPUTE_BF16_REFINE
@@ -311,63 +309,57 @@ class PreparedBank:
                 ad["left"] -= 1
                 flags |= _lib.EPI_REFINE_EXACT
         self.last_match_forced_exact = forced
-        with _on(dev):
-            if raw is not None:
-                rc = lib.manet_global_match_refine(raw.data_ptr(), _emb_code(raw), raw.stride(0), raw.stride(1), qry.data_ptr(),
-                                                   self.ws.data_ptr(), N, self.M0, C, self.n_ids, out.data_ptr(), mem_ptr,
-                                                   flags, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-            else:
-                rc = lib.manet_global_match_prepared_ex(qry.data_ptr(), q_code, q_s0, q_s1,
-                                                        self.ws.data_ptr(), N, self.M0, C, self.n_ids,
-                                                        k_nearest_neighbors, self.compute, out.data_ptr(), mem_ptr,
-                                                        flags, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
         if adapt and not forced:
             ad["seen"] = ad.get("seen", 0) + 1
-        if rc == 0 and adapt and not forced and ad["event"] is None and (ad["seen"] - 1) % self.ADAPT_PROBE_EVERY == 0:
+        try:
+            with _on(dev):
+                if raw is not None:
+                    _lib.call("manet_global_match_refine", raw.data_ptr(), _emb_code(raw), *raw.stride(), qry.data_ptr(),
+                              self.ws.data_ptr(), N, self.M0, C, self.n_ids, out.data_ptr(), mem_ptr, flags, ws.data_ptr(),
+                              ws.numel(), _stream_ptr(dev))
+                else:
+                    _lib.call("manet_global_match_prepared_ex", qry.data_ptr(), q_code, q_s0, q_s1, self.ws.data_ptr(), N, self.M0,
+                              C, self.n_ids, k_nearest_neighbors, self.compute, out.data_ptr(), mem_ptr, flags, ws.data_ptr(),
+                              ws.numel(), _stream_ptr(dev))
+        except RuntimeError:
+            if armed:
+                # the armed workspace is only all-0xff again once the finish kernel has run: after a failed call nothing is
+                # known about it -- drop it, the next armed call fills a fresh one
+                _ws_cache.pop((dev.index, _stream_ptr(dev), "match_armed"), None)
+            raise
+        if adapt and not forced and ad["event"] is None and (ad["seen"] - 1) % self.ADAPT_PROBE_EVERY == 0:
             # this frame's rescue share: one tiny launch counts it straight into pinned host memory (device-visible), an event
             # says when it is there -- looked at by a later call, never waited for.  Every ADAPT_PROBE_EVERY-th filtered frame
             # only: a probe costs ~10 us of stream time, and what the share says changes with the clip, not with the frame.
             if ad["host"] is None:
                 ad["host"] = _probe_slot()
             with _on(dev):
-                rc2 = lib.manet_global_match_refine_rescued_async(ws.data_ptr(), N, C, self.n_ids, ad["host"].data_ptr(),
-                                                                  _stream_ptr(dev))
-            _lib.check(rc2, "manet_global_match_refine_rescued_async")
+                _lib.call("manet_global_match_refine_rescued_async", ws.data_ptr(), N, C, self.n_ids, ad["host"].data_ptr(),
+                          _stream_ptr(dev))
             ad["event"] = torch.cuda.Event()
             ad["event"].record(torch.cuda.current_stream(dev))  # (the stream the launches above went to: _stream_ptr(dev))
-        if rc != 0 and armed:
-            # the armed workspace is only all-0xff again once the finish kernel has run: after a failed call nothing is
-            # known about it -- drop it, the next armed call fills a fresh one
-            _ws_cache.pop((dev.index, _stream_ptr(dev), "match_armed"), None)
-        _lib.check(rc, "manet_global_match_prepared_ex")
         return out
 
     def refine_stats(self):
         """compute='bf16r': (candidate rows the filter pass appended, 1 if the candidate list overflowed and every pair
         scanned its object's rows instead) of the LAST match() on this bank; synchronises."""
-        import ctypes
         if self.compute != _lib.COMPUTE_BF16_REFINE or getattr(self, "_last", None) is None:
             raise RuntimeError("refine_stats: no compute='bf16r' match has run on this bank")
         ws, N = self._last
         torch.cuda.current_stream(ws.device).synchronize()  # (the C call copies on the null stream, which torch's side streams do not block)
-        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
-        _lib.check(_lib.load().manet_global_match_refine_stats(ws.data_ptr(), N, self.C, self.n_ids, ctypes.byref(a),
-                                                               ctypes.byref(b)), "manet_global_match_refine_stats")
-        return a.value, b.value
+        return _lib.query("manet_global_match_refine_stats", ws.data_ptr(), N, self.C, self.n_ids, out=(ctypes.c_int64,) * 2)
 
     def refine_stats_full(self):
         """compute='bf16r', the LAST match() on this bank (synchronises): dict with the candidate rows the filter pass
         listed, the overflow flag, and how many of the frame's 256-query tiles went through the rescue pass (the exact fp32
         kernel) -- `rescued_tile_fraction` is the distribution-dependent part of this mode's cost.  (The figures live in the
         stream-shared match workspace: read them before another bf16r match runs on this stream.)"""
-        import ctypes
         if self.compute != _lib.COMPUTE_BF16_REFINE or getattr(self, "_last", None) is None:
             raise RuntimeError("refine_stats: no compute='bf16r' match has run on this bank")
         ws, N = self._last
         torch.cuda.current_stream(ws.device).synchronize()  # (as refine_stats)
         s4 = (ctypes.c_int64 * 4)()
-        _lib.check(_lib.load().manet_global_match_refine_stats2(ws.data_ptr(), N, self.C, self.n_ids, s4),
-                   "manet_global_match_refine_stats2")
+        _lib.call("manet_global_match_refine_stats2", ws.data_ptr(), N, self.C, self.n_ids, s4)
         return {"candidate_rows": int(s4[0]), "candidate_rows_per_pair": s4[0] / float(N * self.n_ids),
                 "list_overflowed": int(s4[1]), "rescued_tiles": int(s4[2]), "query_tiles": int(s4[3]),
                 "rescued_tile_fraction": s4[2] / float(max(1, s4[3]))}
@@ -379,18 +371,13 @@ class PackedQuery:
     interaction rounds without a per-frame pack pass."""
 
     def __init__(self, query_embeddings, compute="f32"):
-        import ctypes
         _refuse_autograd("PackedQuery", query_embeddings)
-        lib = _lib.load()
         qry, N, C = _flat(query_embeddings, "query_embeddings")
         self.N, self.C, self.compute = N, C, COMPUTE[compute]
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(lib.manet_query_pack_bytes(N, C, self.compute, ctypes.byref(nbytes)), "manet_query_pack_bytes")
-        self.image = torch.empty(nbytes.value, dtype=torch.uint8, device=qry.device)
+        self.image = torch.empty(_lib.query("manet_query_pack_bytes", N, C, self.compute), dtype=torch.uint8, device=qry.device)
         with _on(qry.device):
-            rc = lib.manet_query_pack(qry.data_ptr(), _emb_code(qry), qry.stride(0), qry.stride(1), N, C, self.compute,
-                                      self.image.data_ptr(), self.image.numel(), _stream_ptr(qry.device))
-        _lib.check(rc, "manet_query_pack")
+            _lib.call("manet_query_pack", qry.data_ptr(), _emb_code(qry), *qry.stride(), N, C, self.compute,
+                      self.image.data_ptr(), self.image.numel(), _stream_ptr(qry.device))
         self.device = qry.device
         self.raw = query_embeddings  # (compute="bf16r": the exact re-rank reads the embedding itself)
 
@@ -411,11 +398,7 @@ class PreparedFrame:
 
 
 def frame_workspace_bytes(h, w, C, compute="f32", max_distance=-1):
-    import ctypes
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(_lib.load().manet_frame_workspace_bytes(h, w, C, COMPUTE[compute], max_distance, ctypes.byref(nbytes)),
-               "manet_frame_workspace_bytes")
-    return nbytes.value
+    return _lib.query("manet_frame_workspace_bytes", h, w, C, COMPUTE[compute], max_distance)
 
 
 def prepare_frames(embeddings, compute="f32", max_distance=-1, preset=None, preset_value=1.0):
@@ -423,7 +406,6 @@ def prepare_frames(embeddings, compute="f32", max_distance=-1, preset=None, pres
     IntVOS.py:578-581) in float32 / bfloat16 storage, any strides: ONE launch for the whole batch.  Returns a
     PreparedFrame (one frame) or a list of them.  `preset`: an optional contiguous float32 tensor set to `preset_value`
     by the same launch (the next local match's `out`, see local_match_frames)."""
-    lib = _lib.load()
     _need_gpu(embeddings, "embeddings")
     _refuse_autograd("prepare_frames", embeddings)
     emb = _emb(embeddings)
@@ -447,10 +429,9 @@ def prepare_frames(embeddings, compute="f32", max_distance=-1, preset=None, pres
         fill_ptr, fill_words = preset.data_ptr(), preset.numel()
         fill_bits = struct.unpack("<I", struct.pack("<f", float(preset_value)))[0]
     with _on(emb.device):
-        rc = lib.manet_frame_prepare(emb.data_ptr(), _emb_code(emb), emb.stride(0), emb.stride(2), emb.stride(3),
-                                     emb.stride(1), B, h, w, C, cmp_, max_distance, ws.data_ptr(), per, fill_ptr,
-                                     fill_words, fill_bits, _stream_ptr(emb.device))
-    _lib.check(rc, "manet_frame_prepare")
+        _lib.call("manet_frame_prepare", emb.data_ptr(), _emb_code(emb), emb.stride(0), emb.stride(2), emb.stride(3),
+                  emb.stride(1), B, h, w, C, cmp_, max_distance, ws.data_ptr(), per, fill_ptr, fill_words, fill_bits,
+                  _stream_ptr(emb.device))
     frames = [PreparedFrame(ws[i], h, w, C, cmp_, max_distance, raw=emb[i].permute(1, 2, 0)) for i in range(B)]
     return frames[0] if single else frames
 
@@ -460,7 +441,6 @@ def embed_finish(conv_out, scale, shift, relu=True, emb_dtype=torch.float32, com
     conv_out [B, C, h, w] float32 = embedding_conv's raw output; scale / shift [C] = eval-mode bn2 folded (ops.fold_bn).
     ONE launch -> (embedding [B, C, h, w] in emb_dtype = relu(conv_out * scale + shift), list of PreparedFrames made from the
     embedding as stored -- bit-identical to prepare_frames(embedding))."""
-    lib = _lib.load()
     _need_gpu(conv_out, "conv_out")
     _refuse_autograd("embed_finish", conv_out, scale, shift)
     if conv_out.dim() != 4 or conv_out.dtype != torch.float32:
@@ -478,10 +458,9 @@ def embed_finish(conv_out, scale, shift, relu=True, emb_dtype=torch.float32, com
     per = frame_workspace_bytes(h, w, C, compute, max_distance)
     ws = torch.empty((B, per), dtype=torch.uint8, device=conv_out.device)
     with _on(conv_out.device):
-        rc = lib.manet_embed_finish(conv_out.data_ptr(), conv_out.stride(0), conv_out.stride(2), conv_out.stride(3),
-                                    conv_out.stride(1), scale.data_ptr(), shift.data_ptr(), int(bool(relu)), emb.data_ptr(),
-                                    _emb_code(emb), B, h, w, C, cmp_, max_distance, ws.data_ptr(), per, _stream_ptr(conv_out.device))
-    _lib.check(rc, "manet_embed_finish")
+        _lib.call("manet_embed_finish", conv_out.data_ptr(), conv_out.stride(0), conv_out.stride(2), conv_out.stride(3),
+                  conv_out.stride(1), scale.data_ptr(), shift.data_ptr(), int(bool(relu)), emb.data_ptr(), _emb_code(emb), B, h, w,
+                  C, cmp_, max_distance, ws.data_ptr(), per, _stream_ptr(conv_out.device))
     frames = [PreparedFrame(ws[i], h, w, C, cmp_, max_distance, raw=emb[i].permute(1, 2, 0)) for i in range(B)]
     return emb, frames
 
@@ -490,26 +469,26 @@ def local_match_frames(prev_frame, cur_frame, prev_frame_labels, n_ids, out=None
     """local_previous_frame_nearest_neighbor_features_per_object (IntVOS.py:345-434, downsample configuration) on two
     PreparedFrames: the fused window / min kernel alone -> [h, w, n_ids]; bit-identical to local_match on the
     embeddings the frames were prepared from."""
-    lib = _lib.load()
     a, b = prev_frame, cur_frame
     if (a.h, a.w, a.C, _image_kind(a.compute), a.max_distance) != (b.h, b.w, b.C, _image_kind(b.compute), b.max_distance):
         raise ValueError("the two frames were prepared for different shapes / arithmetic / window radius")
     if b.max_distance < 0:
         raise ValueError("the frames were prepared without a pooled plane (max_distance < 0)")
-    lab = _labels(prev_frame_labels, "prev_frame_labels")
-    if lab.numel() != b.h * b.w:
-        raise ValueError("prev_frame_labels must have height*width entries")
-    dev = b.device
+    return _local_match_tail("manet_local_match_frames", a.ws, b, prev_frame_labels, n_ids, out, out_is_preset)
+
+
+def _local_match_tail(symbol, source, b, prev_frame_labels, n_ids, out, out_is_preset):
+    """the masked minimum of the local match over `source` (the previous PreparedFrame's workspace, or a stored volume) and the
+    current PreparedFrame `b` -> [h, w, n_ids], into `out` if given"""
+    lab =_labels(prev_frame_labels, "prev_frame_labels", b.h * b.w)
     if out is None:
-        out = torch.empty((b.h, b.w, n_ids), dtype=torch.float32, device=dev)
+        out = torch.empty((b.h, b.w, n_ids), dtype=torch.float32, device=b.device)
         out_is_preset = False
     elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != b.h * b.w * n_ids:
         raise ValueError("out must be a contiguous float32 tensor of h*w*n_ids elements")
-    with _on(dev):
-        rc = lib.manet_local_match_frames(a.ws.data_ptr(), b.ws.data_ptr(), lab.data_ptr(), b.h, b.w, b.C, b.compute,
-                                          n_ids, b.max_distance, out.data_ptr(), int(bool(out_is_preset)),
-                                          _stream_ptr(dev))
-    _lib.check(rc, "manet_local_match_frames")
+    with _on(b.device):
+        _lib.call(symbol, source.data_ptr(), b.ws.data_ptr(), lab.data_ptr(), b.h, b.w, b.C, b.compute, n_ids, b.max_distance,
+                  out.data_ptr(), int(bool(out_is_preset)), _stream_ptr(b.device))
     return out.view(b.h, b.w, n_ids)
 
 
@@ -526,11 +505,7 @@ def _volume_suffix(dtype):
 def local_volume_bytes(h, w, max_distance, dtype=torch.float32):
     """bytes of one frame pair's stored window-distance volume (manet_local_volume_bytes; torch.float16: the half-precision
     storage type, manet_local_volume_bytes_f16 -- at most half the fp32 bytes plus one 1 KiB piece)"""
-    import ctypes
-    name = "manet_local_volume_bytes" + _volume_suffix(dtype)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(getattr(_lib.load(), name)(h, w, max_distance, ctypes.byref(nbytes)), name)
-    return nbytes.value
+    return _lib.query("manet_local_volume_bytes" + _volume_suffix(dtype), h, w, max_distance)
 
 
 def local_volumes(prev_frames, cur_frames, out=None, dtype=torch.float32):
@@ -540,8 +515,6 @@ def local_volumes(prev_frames, cur_frames, out=None, dtype=torch.float32):
     optional contiguous tensor of that dtype and shape to write into.  dtype=torch.float16 (opt-in): the fp32 arithmetic, then
     every distance rounded once to half (to nearest even) -- half the bytes; local_match_volume on such a row stays within
     min(2^-12, 2^-11 * value) of the float32 route."""
-    import ctypes
-    lib = _lib.load()
     sfx = _volume_suffix(dtype)
     n = len(cur_frames)
     if len(prev_frames) != n:
@@ -566,10 +539,8 @@ def local_volumes(prev_frames, cur_frames, out=None, dtype=torch.float32):
     pv = arr(*[f.ws.data_ptr() for f in prev_frames])
     cv = arr(*[f.ws.data_ptr() for f in cur_frames])
     vv = arr(*[out[i].data_ptr() for i in range(n)])
-    name = "manet_local_volume_frames" + sfx
     with _on(b.device):
-        rc = getattr(lib, name)(pv, cv, vv, n, b.h, b.w, b.C, b.compute, b.max_distance, _stream_ptr(b.device))
-    _lib.check(rc, name)
+        _lib.call("manet_local_volume_frames" + sfx, pv, cv, vv, n, b.h, b.w, b.C, b.compute, b.max_distance, _stream_ptr(b.device))
     return out
 
 
@@ -577,48 +548,26 @@ def local_match_volume(volume, cur_frame, prev_frame_labels, n_ids, out=None, ou
     """The label-dependent tail of the local match (IntVOS.py:398-432) on a stored volume (one row of local_volumes) -> [h, w,
     n_ids]; on a float32 row bit-identical to local_match_frames(prev_frame, cur_frame, ...) on the pair the volume was made
     from, on a float16 row (dispatch on volume.dtype) bit-identical to this function on the float32 row rounded to half."""
-    lib = _lib.load()
     b = cur_frame
     if b.max_distance < 0:
         raise ValueError("the frame was prepared without a pooled plane (max_distance < 0)")
     if (volume.dtype not in _VOLUME_SUFFIX or not volume.is_contiguous() or volume.device != b.device
             or volume.numel() * volume.element_size() != local_volume_bytes(b.h, b.w, b.max_distance, volume.dtype)):
         raise ValueError("volume must be one contiguous float32 (or float16) row of local_volumes() for this frame geometry")
-    name = "manet_local_match_volume" + _VOLUME_SUFFIX[volume.dtype]
-    lab = _labels(prev_frame_labels, "prev_frame_labels")
-    if lab.numel() != b.h * b.w:
-        raise ValueError("prev_frame_labels must have height*width entries")
-    dev = b.device
-    if out is None:
-        out = torch.empty((b.h, b.w, n_ids), dtype=torch.float32, device=dev)
-        out_is_preset = False
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != b.h * b.w * n_ids:
-        raise ValueError("out must be a contiguous float32 tensor of h*w*n_ids elements")
-    with _on(dev):
-        rc = getattr(lib, name)(volume.data_ptr(), b.ws.data_ptr(), lab.data_ptr(), b.h, b.w, b.C, b.compute, n_ids,
-                                b.max_distance, out.data_ptr(), int(bool(out_is_preset)), _stream_ptr(dev))
-    _lib.check(rc, name)
-    return out.view(b.h, b.w, n_ids)
+    return _local_match_tail("manet_local_match_volume" + _VOLUME_SUFFIX[volume.dtype], volume, b, prev_frame_labels, n_ids, out,
+                             out_is_preset)
 
 
 def normalize_merge_(x, mem=None, normalize=True):
     """In place: x = (sigmoid(x)-0.5)*2 if normalize; if mem: x = mem = min(x, mem)
     (IntVOS.py:611-612, :620-622, :718-723)."""
     _refuse_autograd("normalize_merge_", x, mem)
-    lib = _lib.load()
     _need_gpu(x, "x")
     if x.dtype != torch.float32 or not x.is_contiguous():
         raise ValueError("x must be contiguous float32")
-    mem_ptr = None
-    if mem is not None:
-        _need_gpu(mem, "mem")
-        if mem.dtype != torch.float32 or not mem.is_contiguous() or mem.numel() != x.numel():
-            raise ValueError("mem must be contiguous float32 with x's element count")
-        mem_ptr = mem.data_ptr()
+    mem_ptr = _mem_ptr(mem, x.numel())
     with _on(x.device):
-        rc = lib.manet_normalize_merge_f32(x.data_ptr(), mem_ptr, x.numel(), int(bool(normalize)),
-                                           _stream_ptr(x.device))
-    _lib.check(rc, "manet_normalize_merge_f32")
+        _lib.call("manet_normalize_merge_f32", x.data_ptr(), mem_ptr, x.numel(), int(bool(normalize)), _stream_ptr(x.device))
     return x
 
 
@@ -633,8 +582,6 @@ def _hwc(t, name, allow_bf16=False):
 
 def local_dist(x, y, max_distance, downsample=True):
     """local_pairwise_distances2(x=query, y=prev) (IntVOS.py:266-315) -> [h, w, (2d+1)^2]."""
-    import ctypes
-    lib = _lib.load()
     _refuse_autograd("local_dist", x, y)
     x = _hwc(x, "x")
     y = _hwc(y, "y")
@@ -643,17 +590,11 @@ def local_dist(x, y, max_distance, downsample=True):
         raise ValueError("x and y must have the same shape")
     dev = x.device
     P = 2 * max_distance + 1
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.manet_local_workspace_bytes(h, w, C, max_distance, int(bool(downsample)),
-                                               ctypes.byref(nbytes)), "manet_local_workspace_bytes")
-    ws = _workspace(dev, "local", nbytes.value)
+    ws = _workspace(dev, "local", _lib.query("manet_local_workspace_bytes", h, w, C, max_distance, int(bool(downsample))))
     out = torch.empty((h, w, P * P), dtype=torch.float32, device=dev)
     with _on(dev):
-        rc = lib.manet_local_dist_f32(x.data_ptr(), x.stride(0), x.stride(1), x.stride(2), y.data_ptr(),
-                                      y.stride(0), y.stride(1), y.stride(2), h, w, C, max_distance,
-                                      int(bool(downsample)), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      _stream_ptr(dev))
-    _lib.check(rc, "manet_local_dist_f32")
+        _lib.call("manet_local_dist_f32", *_strided(x), *_strided(y), h, w, C, max_distance, int(bool(downsample)),
+                  out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
     return out
 
 
@@ -662,66 +603,42 @@ def local_match(prev_frame_embedding, query_embedding, prev_frame_labels, n_ids,
     """local_previous_frame_nearest_neighbor_features_per_object (IntVOS.py:345-434) -> [h, w, n_ids].
     deterministic=True: when the call is differentiated, the ordered training route (csrc/match_train.hip): the same forward
     bits, a sparse backward without float atomics (the same gradient bits on every run)."""
-    import ctypes
-    lib = _lib.load()
-    if _wants_grad(prev_frame_embedding, query_embedding):
-        from .autograd import LocalMatchFn, LocalMatchFullFn, LocalMatchOrderedFn, LocalMatchFullOrderedFn
-        if deterministic:
-            LocalMatchFn, LocalMatchFullFn = LocalMatchOrderedFn, LocalMatchFullOrderedFn
-        prev = _hwc(prev_frame_embedding, "prev_frame_embedding")
-        cur = _hwc(query_embedding, "query_embedding")
-        if tuple(prev.shape) != tuple(cur.shape):
-            raise ValueError("prev_frame_embedding and query_embedding must have the same shape")
-        lab = _labels(prev_frame_labels, "prev_frame_labels")
-        if lab.numel() != cur.shape[0] * cur.shape[1]:
-            raise ValueError("prev_frame_labels must have height*width entries")
-        return (LocalMatchFn if downsample else LocalMatchFullFn).apply(prev, cur, lab, n_ids, max_distance)
-    both_bf16 = (prev_frame_embedding.dtype == torch.bfloat16 and query_embedding.dtype == torch.bfloat16
-                 and downsample)  # 2-byte embeddings are read as they are by the pooling pass
+    grad = _wants_grad(prev_frame_embedding, query_embedding)
+    both_bf16 = (not grad and prev_frame_embedding.dtype == torch.bfloat16 and query_embedding.dtype == torch.bfloat16
+                 and downsample)  # 2-byte embeddings are read as they are by the pooling pass (the training route is fp32)
     prev = _hwc(prev_frame_embedding, "prev_frame_embedding", both_bf16)
     cur = _hwc(query_embedding, "query_embedding", both_bf16)
     h, w, C = cur.shape
     if tuple(prev.shape) != (h, w, C):
         raise ValueError("prev_frame_embedding and query_embedding must have the same shape")
-    lab = _labels(prev_frame_labels, "prev_frame_labels")
-    if lab.numel() != h * w:
-        raise ValueError("prev_frame_labels must have height*width entries")
+    lab = _labels(prev_frame_labels, "prev_frame_labels", h * w)
+    if grad:
+        from .autograd import LocalMatchFn, LocalMatchFullFn, LocalMatchOrderedFn, LocalMatchFullOrderedFn
+        if deterministic:
+            LocalMatchFn, LocalMatchFullFn = LocalMatchOrderedFn, LocalMatchFullOrderedFn
+        return (LocalMatchFn if downsample else LocalMatchFullFn).apply(prev, cur, lab, n_ids, max_distance)
     dev = cur.device
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(lib.manet_local_workspace_bytes(h, w, C, max_distance, int(bool(downsample)),
-                                               ctypes.byref(nbytes)), "manet_local_workspace_bytes")
-    ws = _workspace(dev, "local", nbytes.value)
+    ws = _workspace(dev, "local", _lib.query("manet_local_workspace_bytes", h, w, C, max_distance, int(bool(downsample))))
     out = torch.empty((h, w, n_ids), dtype=torch.float32, device=dev)
     with _on(dev):
-        rc = lib.manet_local_match_ex(prev.data_ptr(), prev.stride(0), prev.stride(1), prev.stride(2),
-                                      cur.data_ptr(), cur.stride(0), cur.stride(1), cur.stride(2), _emb_code(cur),
-                                      lab.data_ptr(), h, w, C, n_ids, max_distance, int(bool(downsample)),
-                                      out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "manet_local_match_ex")
+        _lib.call("manet_local_match_ex", *_strided(prev), *_strided(cur), _emb_code(cur), lab.data_ptr(), h, w, C, n_ids,
+                  max_distance, int(bool(downsample)), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
     return out
 
 
 def correlation_out_dims(H, W, pad_size, kernel_size, max_displacement, stride1, stride2):
-    import ctypes
-    lib = _lib.load()
-    oc, oh, ow = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    _lib.check(lib.manet_correlation_out_dims(H, W, pad_size, kernel_size, max_displacement, stride1, stride2,
-                                              ctypes.byref(oc), ctypes.byref(oh), ctypes.byref(ow)),
-               "manet_correlation_out_dims")
-    return oc.value, oh.value, ow.value
+    return _lib.query("manet_correlation_out_dims", H, W, pad_size, kernel_size, max_displacement, stride1, stride2,
+                      out=(ctypes.c_int,) * 3)
 
 
 def correlation_forward(input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2):
     """correlation_cuda.forward (correlation_cuda.cc:10-87) -> [B, (2r+1)^2, outH, outW] in the inputs' dtype
     (float32 / float16 / float64; anything else is computed in float32)."""
-    lib = _lib.load()
-    if _wants_grad(input1, input2):
-        from .autograd import CorrelationFn
-        _need_gpu(input1, "input1")
-        _need_gpu(input2, "input2")
-        return CorrelationFn.apply(input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2)
     _need_gpu(input1, "input1")
     _need_gpu(input2, "input2")
+    if _wants_grad(input1, input2):
+        from .autograd import CorrelationFn
+        return CorrelationFn.apply(input1, input2, pad_size, kernel_size, max_displacement, stride1, stride2)
     # the reference's forward dispatches float / double / half (correlation_cuda_kernel.cu:386-415)
     code = {torch.float32: 0, torch.float16: 1, torch.float64: 2}.get(input1.dtype)
     if code is None or input2.dtype != input1.dtype:
@@ -734,10 +651,8 @@ def correlation_forward(input1, input2, pad_size, kernel_size, max_displacement,
     oc, oh, ow = correlation_out_dims(H, W, pad_size, kernel_size, max_displacement, stride1, stride2)
     out = torch.empty((B, oc, oh, ow), dtype=a.dtype, device=a.device)
     with _on(a.device):
-        rc = lib.manet_correlation_forward(a.data_ptr(), b.data_ptr(), code, B, C, H, W, pad_size, kernel_size,
-                                           max_displacement, stride1, stride2, out.data_ptr(),
-                                           _stream_ptr(a.device))
-    _lib.check(rc, "manet_correlation_forward")
+        _lib.call("manet_correlation_forward", a.data_ptr(), b.data_ptr(), code, B, C, H, W, pad_size, kernel_size,
+                  max_displacement, stride1, stride2, out.data_ptr(), _stream_ptr(a.device))
     return out
 
 
@@ -746,7 +661,6 @@ def upsample_argmax(logits, size, want_small=True):
     bilinear(align_corners) upsample of `logits` [1, n_ids, h, w] to `size`=(H, W) + argmax over ids
     (test.py:253-255) -> int64 [1, H, W]; and that mask nearest-resized back to (h, w) as the next
     frame's previous-frame label (IntVOS.py:598-599) -> int32 [1, 1, h, w] (None if not wanted)."""
-    lib = _lib.load()
     _need_gpu(logits, "logits")
     # integer outputs (argmax): nothing to differentiate, same as the reference's torch.argmax
     if logits.dim() != 4 or logits.shape[0] != 1:
@@ -757,16 +671,13 @@ def upsample_argmax(logits, size, want_small=True):
     mask = torch.empty((1, H, W), dtype=torch.int64, device=lg.device)
     small = torch.empty((1, 1, h, w), dtype=torch.int32, device=lg.device) if want_small else None
     with _on(lg.device):
-        rc = lib.manet_upsample_argmax(lg.data_ptr(), n_ids, h, w, H, W, mask.data_ptr(),
-                                       None if small is None else small.data_ptr(), _stream_ptr(lg.device))
-    _lib.check(rc, "manet_upsample_argmax")
+        _lib.call("manet_upsample_argmax", lg.data_ptr(), n_ids, h, w, H, W, mask.data_ptr(), _ptr(small), _stream_ptr(lg.device))
     return mask, small
 
 
 def label_resize_nearest(mask, size):
     """F.interpolate(mask.float(), size=(h, w), mode='nearest').int() (IntVOS.py:598-599) in one launch.
     mask: integer [1, 1, H, W] (or [1, H, W] / [H, W]) -> int32 [1, 1, h, w]."""
-    lib = _lib.load()
     _need_gpu(mask, "mask")
     if mask.is_floating_point() or mask.numel() != mask.shape[-1] * mask.shape[-2]:
         raise ValueError("mask must be ONE integer image [.., H, W]")
@@ -775,8 +686,7 @@ def label_resize_nearest(mask, size):
     h, w = int(size[0]), int(size[1])
     out = torch.empty((1, 1, h, w), dtype=torch.int32, device=m.device)
     with _on(m.device):
-        rc = lib.manet_label_resize_nearest(m.data_ptr(), H, W, h, w, out.data_ptr(), _stream_ptr(m.device))
-    _lib.check(rc, "manet_label_resize_nearest")
+        _lib.call("manet_label_resize_nearest", m.data_ptr(), H, W, h, w, out.data_ptr(), _stream_ptr(m.device))
     return out
 
 
@@ -785,7 +695,6 @@ def frame_begin(mask, size, fill=None, fill_value=1.0, scalar_dst=None, scalar_v
     contiguous float32 tensor) := fill_value -- the local map's slot pre-set for the wide windows -- and the one-element float32
     tensor `scalar_dst` := scalar_value -- the frame's distance weight in the caller's table (IntVOS.py:641).  Each was a ~5 us
     launch of its own in a propagated frame.  Returns the int32 [1, 1, h, w] label."""
-    lib = _lib.load()
     _need_gpu(mask, "mask")
     if mask.is_floating_point() or mask.numel() != mask.shape[-1] * mask.shape[-2]:
         raise ValueError("mask must be ONE integer image [.., H, W]")
@@ -797,10 +706,8 @@ def frame_begin(mask, size, fill=None, fill_value=1.0, scalar_dst=None, scalar_v
             raise ValueError("%s must be a contiguous float32 tensor on the mask's device%s" % (name, "" if n is None else " with one element"))
     out = torch.empty((1, 1, h, w), dtype=torch.int32, device=m.device)
     with _on(m.device):
-        rc = lib.manet_frame_begin(m.data_ptr(), H, W, h, w, out.data_ptr(), None if fill is None else fill.data_ptr(),
-                                   0 if fill is None else fill.numel(), float(fill_value),
-                                   None if scalar_dst is None else scalar_dst.data_ptr(), float(scalar_value), _stream_ptr(m.device))
-    _lib.check(rc, "manet_frame_begin")
+        _lib.call("manet_frame_begin", m.data_ptr(), H, W, h, w, out.data_ptr(), _ptr(fill), 0 if fill is None else fill.numel(),
+                  float(fill_value), _ptr(scalar_dst), float(scalar_value), _stream_ptr(m.device))
     return out
 
 
@@ -810,7 +717,6 @@ def head_layer1_object(global_map, local_map, labels, n_ids, size, dw_weight, dw
     (IntVOS.py:663-669) -> depthwise 7x7 + bn1 + relu1 -> 1x1 (3 -> 256, bn2 folded) + `term` (the shared-embedding half,
     [1, 256, h, w]) [+ relu2] -> [n_ids, 256, h, w].  The same bits as head_inputs + dwconv7x7_bn_relu + conv1x1_mfma(add=term)."""
     _refuse_autograd("head_layer1_object", global_map, local_map, term)
-    lib = _lib.load()
     _need_gpu(global_map, "global_map")
     h, w = int(size[0]), int(size[1])
     lab = labels.to(torch.int32).contiguous()
@@ -834,11 +740,9 @@ def head_layer1_object(global_map, local_map, labels, n_ids, size, dw_weight, dw
         raise ValueError("n_ids must be positive")
     out = torch.empty((n_ids, PW_COUT, h, w), dtype=torch.float32, device=g.device)
     with _on(g.device):
-        rc = lib.manet_head_layer1_object_f32(g.data_ptr(), l.data_ptr(), lab.data_ptr(), h, w, n_ids, wd.data_ptr(),
-                                              None if db is None else db.data_ptr(), None if sc is None else sc.data_ptr(),
-                                              None if sh is None else sh.data_ptr(), w2.data_ptr(), bb.data_ptr(), tm.data_ptr(),
-                                              int(bool(relu_out)), out.data_ptr(), _stream_ptr(g.device))
-    _lib.check(rc, "manet_head_layer1_object_f32")
+        _lib.call("manet_head_layer1_object_f32", g.data_ptr(), l.data_ptr(), lab.data_ptr(), h, w, n_ids, wd.data_ptr(), _ptr(db),
+                  _ptr(sc), _ptr(sh), w2.data_ptr(), bb.data_ptr(), tm.data_ptr(), int(bool(relu_out)), out.data_ptr(),
+                  _stream_ptr(g.device))
     return out
 
 
@@ -847,7 +751,6 @@ def head_inputs(global_map, local_map, labels, n_ids, size):
     [n_ids, 3, h, w] = (global map of o, local map of o, labels == o), size = (h, w); global_map / local_map hold
     h*w*n_ids elements laid out [h, w, n_ids] (any view shape), labels h*w integers."""
     _refuse_autograd("head_inputs", global_map, local_map)
-    lib = _lib.load()
     _need_gpu(global_map, "global_map")
     lab = labels.to(torch.int32).contiguous()
     h, w = int(size[0]), int(size[1])
@@ -856,9 +759,8 @@ def head_inputs(global_map, local_map, labels, n_ids, size):
     g, l = global_map.float().contiguous(), local_map.float().contiguous()
     out = torch.empty((n_ids, 3, h, w), dtype=torch.float32, device=g.device)
     with _on(g.device):
-        rc = lib.manet_head_inputs_f32(g.data_ptr(), l.data_ptr(), lab.data_ptr(), h * w, n_ids, out.data_ptr(),
-                                       _stream_ptr(g.device))
-    _lib.check(rc, "manet_head_inputs_f32")
+        _lib.call("manet_head_inputs_f32", g.data_ptr(), l.data_ptr(), lab.data_ptr(), h * w, n_ids, out.data_ptr(),
+                  _stream_ptr(g.device))
     return out
 
 
@@ -878,7 +780,6 @@ def dwconv7x7_bn_relu(x, weight, bias=None, bn=None, relu=True, scale=None, shif
     `scale` / `shift` (fold_bn), or neither.  relu_in: read the input through max(x, 0) (the preceding block's
     relu2 folded into this pass)."""
     _refuse_autograd("dwconv7x7_bn_relu", x, weight, bias, scale, shift)  # callers use it under no_grad only
-    lib = _lib.load()
     _need_gpu(x, "x")
     x = x.float().contiguous()
     B, C, h, w = x.shape
@@ -892,12 +793,8 @@ def dwconv7x7_bn_relu(x, weight, bias=None, bn=None, relu=True, scale=None, shif
     bz = None if bias is None else bias.detach().float().contiguous()
     out = torch.empty_like(x)
     with _on(x.device):
-        rc = lib.manet_dwconv7x7_bn_relu_ex(x.data_ptr(), B, C, h, w, wt.data_ptr(),
-                                            None if bz is None else bz.data_ptr(),
-                                            None if scale is None else scale.data_ptr(),
-                                            None if shift is None else shift.data_ptr(), int(bool(relu)),
-                                            int(bool(relu_in)), out.data_ptr(), _stream_ptr(x.device))
-    _lib.check(rc, "manet_dwconv7x7_bn_relu_ex")
+        _lib.call("manet_dwconv7x7_bn_relu_ex", x.data_ptr(), B, C, h, w, wt.data_ptr(), _ptr(bz), _ptr(scale), _ptr(shift),
+                  int(bool(relu)), int(bool(relu_in)), out.data_ptr(), _stream_ptr(x.device))
     return out
 
 
@@ -917,15 +814,13 @@ def _dwconv_check(x, weight, bias):
 
 def _dwconv_forward(x, weight, bias):
     """conv + bias on the HIP kernel (manet_dwconv_forward_f32); x, weight contiguous, no autograd"""
-    lib = _lib.load()
     B, C, h, w = x.shape
     K = int(weight.shape[2])
     bz = None if bias is None else bias.detach().contiguous()
     out = torch.empty_like(x)
     with _on(x.device):
-        rc = lib.manet_dwconv_forward_f32(x.data_ptr(), B, C, h, w, K, weight.detach().data_ptr(),
-                                          None if bz is None else bz.data_ptr(), out.data_ptr(), _stream_ptr(x.device))
-    _lib.check(rc, "manet_dwconv_forward_f32")
+        _lib.call("manet_dwconv_forward_f32", x.data_ptr(), B, C, h, w, K, weight.detach().data_ptr(), _ptr(bz), out.data_ptr(),
+                  _stream_ptr(x.device))
     return out
 
 
@@ -954,15 +849,12 @@ def _pw_check(x, weight, bias):
 
 @functools.lru_cache(maxsize=256)
 def _ws_bytes(query, *dims):
-    """size of a workspace query of the C ABI (manet_*_workspace_bytes), per shape: a function of the shape alone"""
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(getattr(_lib.load(), query)(*dims, ctypes.byref(nbytes)), query)
-    return nbytes.value
+    """_lib.query remembered per shape -- only for the workspace queries that are a function of the shape alone (no tuning knob)"""
+    return _lib.query(query, *dims)
 
 
 def _pw_forward(x, weight, bias):
     """W x + bias on the HIP kernels (manet_pw_forward_f32); x, weight contiguous, no autograd"""
-    lib = _lib.load()
     B, Cin, h, w = x.shape
     Cout = int(weight.shape[0])
     bz = None if bias is None else bias.detach().contiguous()
@@ -970,10 +862,8 @@ def _pw_forward(x, weight, bias):
     nbytes = _ws_bytes("manet_pw_forward_workspace_bytes", B, Cin, Cout, h * w)
     with _on(x.device):
         ws = _workspace(x.device, "pw_forward", nbytes) if nbytes else None
-        rc = lib.manet_pw_forward_f32(x.data_ptr(), B, Cin, Cout, h * w, weight.detach().data_ptr(),
-                                      None if bz is None else bz.data_ptr(), out.data_ptr(),
-                                      None if ws is None else ws.data_ptr(), nbytes, _stream_ptr(x.device))
-    _lib.check(rc, "manet_pw_forward_f32")
+        _lib.call("manet_pw_forward_f32", x.data_ptr(), B, Cin, Cout, h * w, weight.detach().data_ptr(), _ptr(bz), out.data_ptr(),
+                  _ptr(ws), nbytes, _stream_ptr(x.device))
     return out
 
 
@@ -998,7 +888,6 @@ def batch_norm_relu_ok(bn):
 def _bn_relu_forward(x, weight, bias, running_mean, running_var, momentum, eps, training):
     """(out, save) of relu(batch_norm(x)) on the HIP kernels (manet_bn_relu_forward_f32), save [2, C] = the mean and invstd
     used; x contiguous"""
-    lib = _lib.load()
     B, C, h, w = x.shape
     dev = x.device
     out = torch.empty_like(x)
@@ -1007,10 +896,9 @@ def _bn_relu_forward(x, weight, bias, running_mean, running_var, momentum, eps, 
     with _on(dev):
         ws = _workspace(dev, "bn_relu", nbytes)
         sp = save.data_ptr()
-        rc = lib.manet_bn_relu_forward_f32(x.data_ptr(), B, C, h * w, weight.data_ptr(), bias.data_ptr(), running_mean.data_ptr(),
-                                           running_var.data_ptr(), float(momentum), float(eps), 1 if training else 0, out.data_ptr(),
-                                           sp, sp + 4 * C, ws.data_ptr(), nbytes, _stream_ptr(dev))
-    _lib.check(rc, "manet_bn_relu_forward_f32")
+        _lib.call("manet_bn_relu_forward_f32", x.data_ptr(), B, C, h * w, weight.data_ptr(), bias.data_ptr(),
+                  running_mean.data_ptr(), running_var.data_ptr(), float(momentum), float(eps), 1 if training else 0,
+                  out.data_ptr(), sp, sp + 4 * C, ws.data_ptr(), nbytes, _stream_ptr(dev))
     return out, save
 
 
@@ -1066,7 +954,6 @@ def conv1x1_mfma(x, w2t, b2, relu_out=False, head_weight=None, head_bias=None, a
     fused into the epilogue -- returns [B, 1, h, w], the 256-channel activation is never written.
     add [256, h, w] / [1, 256, h, w] fp32: added to every batch entry before relu_out (layer1's shared-embedding half)."""
     _refuse_autograd("conv1x1_mfma", x, w2t, b2, head_weight, head_bias, add)
-    lib = _lib.load()
     _need_gpu(x, "x")
     x = x.float().contiguous()
     B, cin, h, w = x.shape
@@ -1083,9 +970,8 @@ def conv1x1_mfma(x, w2t, b2, relu_out=False, head_weight=None, head_bias=None, a
         add = add.contiguous()
         out = torch.empty((B, PW_COUT, h, w), dtype=torch.float32, device=x.device)
         with _on(x.device):
-            rc = lib.manet_conv1x1_add_f32(x.data_ptr(), cin * h * w, B, cin, h * w, w2t.data_ptr(), b2.data_ptr(),
-                                           add.data_ptr(), PW_COUT, int(bool(relu_out)), out.data_ptr(), _stream_ptr(x.device))
-        _lib.check(rc, "manet_conv1x1_add_f32")
+            _lib.call("manet_conv1x1_add_f32", x.data_ptr(), cin * h * w, B, cin, h * w, w2t.data_ptr(), b2.data_ptr(),
+                      add.data_ptr(), PW_COUT, int(bool(relu_out)), out.data_ptr(), _stream_ptr(x.device))
         return out
     if head_weight is not None:
         if head_weight.numel() != PW_COUT:
@@ -1094,16 +980,13 @@ def conv1x1_mfma(x, w2t, b2, relu_out=False, head_weight=None, head_bias=None, a
         hb = None if head_bias is None else head_bias.detach().float().contiguous()
         hout = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
         with _on(x.device):
-            rc = lib.manet_conv1x1_head_f32(x.data_ptr(), cin * h * w, B, cin, h * w, w2t.data_ptr(), b2.data_ptr(), PW_COUT,
-                                            0, None, hw.data_ptr(), None if hb is None else hb.data_ptr(), hout.data_ptr(),
-                                            _stream_ptr(x.device))
-        _lib.check(rc, "manet_conv1x1_head_f32")
+            _lib.call("manet_conv1x1_head_f32", x.data_ptr(), cin * h * w, B, cin, h * w, w2t.data_ptr(), b2.data_ptr(), PW_COUT,
+                      0, None, hw.data_ptr(), _ptr(hb), hout.data_ptr(), _stream_ptr(x.device))
         return hout
     out = torch.empty((B, PW_COUT, h, w), dtype=torch.float32, device=x.device)
     with _on(x.device):
-        rc = lib.manet_conv1x1_f32(x.data_ptr(), cin * h * w, B, cin, h * w, w2t.data_ptr(), b2.data_ptr(), PW_COUT,
-                                   int(bool(relu_out)), out.data_ptr(), _stream_ptr(x.device))
-    _lib.check(rc, "manet_conv1x1_f32")
+        _lib.call("manet_conv1x1_f32", x.data_ptr(), cin * h * w, B, cin, h * w, w2t.data_ptr(), b2.data_ptr(), PW_COUT,
+                  int(bool(relu_out)), out.data_ptr(), _stream_ptr(x.device))
     return out
 
 
@@ -1123,10 +1006,9 @@ class SplitWeight:
         self.cin, self.pieces = int(w2t.shape[0]), int(pieces)
         nbytes, pack = ((lib.manet_conv1x1_x6_weight_bytes, lib.manet_conv1x1_x6_pack) if pieces == 3
                         else (lib.manet_conv1x1_x3_weight_bytes, lib.manet_conv1x1_x3_pack))
-        self.packed = torch.empty(int(nbytes(self.cin)), dtype=torch.uint8, device=w2t.device)
+        self.packed = torch.empty(int(nbytes(self.cin)), dtype=torch.uint8, device=w2t.device)  # (returns the size, not a code)
         with _on(w2t.device):
-            rc = pack(w2t.data_ptr(), self.cin, PW_COUT, self.packed.data_ptr(), _stream_ptr(w2t.device))
-        _lib.check(rc, "manet_conv1x1_x%d_pack" % (3 if pieces == 2 else 6))
+            _lib.call(pack, w2t.data_ptr(), self.cin, PW_COUT, self.packed.data_ptr(), _stream_ptr(w2t.device))
 
 
 def conv1x1_split_ok(x, cout):
@@ -1142,7 +1024,6 @@ def conv1x1_split(x, weight, b2, relu_out=False, add=None, head_weight=None, hea
     add [1, 256, h, w] (or [256, h, w]): added to every batch entry before relu_out -- layer1's shared-embedding half.
     head_weight / head_bias: DynamicSegHead's output layer fused (see conv1x1_mfma) -> [B, 1, h, w]."""
     _refuse_autograd("conv1x1_split", x, b2, add, head_weight, head_bias)
-    lib = _lib.load()
     _need_gpu(x, "x")
     if not isinstance(weight, SplitWeight):
         raise TypeError("weight must be an ops.SplitWeight")
@@ -1168,12 +1049,10 @@ def conv1x1_split(x, weight, b2, relu_out=False, add=None, head_weight=None, hea
         hout = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
     else:
         out = torch.empty((B, PW_COUT, h, w), dtype=torch.float32, device=x.device)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    fn = lib.manet_conv1x1_x6_f32 if weight.pieces == 3 else lib.manet_conv1x1_x3_f32  # (the weight's packing decides)
-    with _on(x.device):
-        rc = fn(x.data_ptr(), cin * h * w, B, cin, h * w, weight.packed.data_ptr(), b2.data_ptr(),
-                ptr(add), PW_COUT, int(bool(relu_out)), ptr(out), ptr(hw), ptr(hb), ptr(hout), _stream_ptr(x.device))
-    _lib.check(rc, "manet_conv1x1_x6_f32" if weight.pieces == 3 else "manet_conv1x1_x3_f32")
+    with _on(x.device):  # (the weight's packing decides the symbol)
+        _lib.call("manet_conv1x1_x6_f32" if weight.pieces == 3 else "manet_conv1x1_x3_f32", x.data_ptr(), cin * h * w, B, cin,
+                  h * w, weight.packed.data_ptr(), b2.data_ptr(), _ptr(add), PW_COUT, int(bool(relu_out)), _ptr(out), _ptr(hw),
+                  _ptr(hb), _ptr(hout), _stream_ptr(x.device))
     return hout if head_weight is not None else out
 
 
@@ -1181,7 +1060,6 @@ def relu_conv1x1_c1(x, weight, bias=None, relu_in=True):
     """DynamicSegHead's output layer in one pass over the activation (IntVOS.py:519,525): Conv2d(C, 1, 1) applied to
     max(x, 0) (relu_in) or to x.  x [B, C, h, w] fp32, weight [1, C, 1, 1], bias [1] or None -> [B, 1, h, w]."""
     _refuse_autograd("relu_conv1x1_c1", x, weight, bias)
-    lib = _lib.load()
     _need_gpu(x, "x")
     x = x.float().contiguous()
     B, C, h, w = x.shape
@@ -1191,9 +1069,8 @@ def relu_conv1x1_c1(x, weight, bias=None, relu_in=True):
     bz = None if bias is None else bias.detach().float().contiguous()
     out = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
     with _on(x.device):
-        rc = lib.manet_relu_conv1x1_c1_f32(x.data_ptr(), B, C, h * w, wt.data_ptr(), None if bz is None else bz.data_ptr(),
-                                           int(bool(relu_in)), out.data_ptr(), _stream_ptr(x.device))
-    _lib.check(rc, "manet_relu_conv1x1_c1_f32")
+        _lib.call("manet_relu_conv1x1_c1_f32", x.data_ptr(), B, C, h * w, wt.data_ptr(), _ptr(bz), int(bool(relu_in)),
+                  out.data_ptr(), _stream_ptr(x.device))
     return out
 
 
@@ -1214,9 +1091,8 @@ def _out_conv_forward(x, weight, bias):
     bz = None if bias is None else bias.detach().contiguous()
     out = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
     with _on(x.device):
-        rc = _lib.load().manet_out_conv_forward_f32(x.data_ptr(), B, C, h * w, weight.detach().data_ptr(),
-                                                    None if bz is None else bz.data_ptr(), out.data_ptr(), _stream_ptr(x.device))
-    _lib.check(rc, "manet_out_conv_forward_f32")
+        _lib.call("manet_out_conv_forward_f32", x.data_ptr(), B, C, h * w, weight.detach().data_ptr(), _ptr(bz), out.data_ptr(),
+                  _stream_ptr(x.device))
     return out
 
 
@@ -1303,8 +1179,7 @@ def _loss_args(logits, labels, size):
                          % (LOSS_MAX_CHANNELS, tuple(logits.shape), logits.dtype, tuple(labels.shape), labels.dtype, size))
     B, C, h, w = logits.shape
     H, W = int(size[0]), int(size[1])
-    return (logits.data_ptr(), logits.stride(0), logits.stride(1), logits.stride(2), logits.stride(3), labels.data_ptr(),
-            labels.element_size(), labels.stride(0), labels.stride(1), labels.stride(2), B, C, h, w, H, W)
+    return (*_strided(logits), labels.data_ptr(), labels.element_size(), *labels.stride(), B, C, h, w, H, W)
 
 
 def upsampled_cross_entropy_pixels(logits, labels, size):
@@ -1316,8 +1191,7 @@ def upsampled_cross_entropy_pixels(logits, labels, size):
     args = _loss_args(logits, labels, size)
     out = torch.empty((logits.shape[0], int(size[0]) * int(size[1])), dtype=torch.float32, device=logits.device)
     with _on(logits.device):
-        rc = _lib.load().manet_loss_ce_pixels_f32(*args, out.data_ptr(), _stream_ptr(logits.device))
-    _lib.check(rc, "manet_loss_ce_pixels_f32")
+        _lib.call("manet_loss_ce_pixels_f32", *args, out.data_ptr(), _stream_ptr(logits.device))
     return out
 
 
@@ -1332,10 +1206,8 @@ def _loss_forward(logits, labels, size, k, divisor):
     nbytes = _ws_bytes("manet_loss_ce_topk_workspace_bytes", B, H, W)
     with _on(dev):
         ws = _workspace(dev, "loss_ce_topk", nbytes)
-        rc = _lib.load().manet_loss_ce_topk_forward_f32(*args, int(k), float(divisor), pix.data_ptr(), loss.data_ptr(), stats.data_ptr(),
-                                                        stats.data_ptr() + 4 * B, stats.data_ptr() + 8 * B, ws.data_ptr(), nbytes,
-                                                        _stream_ptr(dev))
-    _lib.check(rc, "manet_loss_ce_topk_forward_f32")
+        _lib.call("manet_loss_ce_topk_forward_f32", *args, int(k), float(divisor), pix.data_ptr(), loss.data_ptr(), stats.data_ptr(),
+                  stats.data_ptr() + 4 * B, stats.data_ptr() + 8 * B, ws.data_ptr(), nbytes, _stream_ptr(dev))
     return loss, pix, stats
 
 
