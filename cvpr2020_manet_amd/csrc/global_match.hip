@@ -49,52 +49,26 @@ constexpr int META_KMAX = 200;     // [200]      max |k|^2 over the bank's rows,
 // REFINE_SUB by bank size (refine_sub): the pre-pass costs 1 / REFINE_SUB of the filter pass's matrix work; a sparser sample
 // leaves ~ln more candidates per pair for the cheap re-rank -- the larger the bank, the sparser the sample that pays.
 constexpr int META_NAN = 66;       // [66..129]  object o's bank rows contain a NaN (MANET_COMPUTE_BF16_REFINE)
-int refine_sub(long T_max)
-{
-    const int forced = manet_tune_get(MANET_TUNE_REFINE_SUB, 0);  // (experiments)
-    if (forced > 0) return forced;
-    return T_max <= 2500 ? 8 : 16;  // 480p x 5 frames: 2 007 tiles; 720p x 10 frames: 9 006
-}
-#ifndef MANET_REFINE_XCHG_MASK
-#define MANET_REFINE_XCHG_MASK 3
-#endif
-constexpr int REFINE_XCHG_MASK = MANET_REFINE_XCHG_MASK;  // threshold exchange every (mask + 1) steps
-#ifndef MANET_REFINE_CAP
-#define MANET_REFINE_CAP 128
-#endif
-#ifndef MANET_REFINE_LDS_LIST
-#define MANET_REFINE_LDS_LIST 2048
-#endif
-constexpr int REFINE_CAP = MANET_REFINE_CAP;  // capacity of a candidate bucket (one per 32-query block), in rows per (query, object) pair ON AVERAGE
-constexpr int REFINE_LDS_LIST = MANET_REFINE_LDS_LIST;  // candidate entries a filter workgroup collects in LDS before it appends them in bulk
+int refine_sub(long T_max) { return T_max <= 2500 ? 8 : 16; }  // 480p x 5 frames: 2 007 tiles; 720p x 10 frames: 9 006
+constexpr int REFINE_XCHG_MASK = 3;  // threshold exchange every (mask + 1) steps
+constexpr int REFINE_CAP = 128;  // capacity of a candidate bucket (one per 32-query block), in rows per (query, object) pair ON AVERAGE
+constexpr int REFINE_LDS_LIST = 2048;  // candidate entries a filter workgroup collects in LDS before it appends them in bulk
 // A 32-query x 32-row block with more qualifying distances than a sub-list holds is listed as ONE "dense" entry {block's
 // first pair, 0x80000000 | first bank slot of the pass}: the re-rank evaluates all of its 1 024 distances exactly.  At most
 // REFINE_DENSE_CAP of them per 32-query bucket (counted in bcnt's second half); one more marks the bucket incomplete and
 // the rescue pass (the exact fp32 kernel on the 256-query tile) takes over.  A dense entry is one 32 x 32 x C tile on the fp32
 // matrix pipe for ONE wave (1.4 us at C = 100, operands from global memory / LDS per entry): 1 024 of them in every bucket of a
 // 480p frame are ~1.1 ms of the chip, a quarter of the fp32 kernel -- beyond that the fp32 kernel's operand reuse wins.
-#ifndef MANET_REFINE_DENSE_CAP
-#define MANET_REFINE_DENSE_CAP 1024
-#endif
-constexpr int REFINE_DENSE_CAP = MANET_REFINE_DENSE_CAP;
+constexpr int REFINE_DENSE_CAP = 1024;
 constexpr unsigned REFINE_DENSE_BIT = 0x80000000u;
 // ... and a block is listed whole as soon as more than REFINE_DENSE_MIN of its 1 024 distances qualify: a listed row costs the
 // re-rank a 400-byte gather of its bank row (C = 100) per (query, row) pair, a dense entry 12.8 KB of rows per 1 024 pairs and
 // 1.4 us of one wave's matrix pipe (more when the wave has nothing else to hide the row loads behind).  Measured on one box,
 // ms per step on video-like / smooth embeddings at cfg2 size for (REFINE_DENSE_MIN, REFINE_DENSE_LANES): (128, off) 0.798 /
 // 0.963, (64, 24) 0.799 / 0.866, (64, 16) 0.803 / 0.856, (32, 16) 0.806 / 0.858, (32, 8) 0.813 / 0.854.
-#ifndef MANET_REFINE_DENSE_MIN
-#define MANET_REFINE_DENSE_MIN 64
-#endif
-constexpr int REFINE_DENSE_MIN = MANET_REFINE_DENSE_MIN;
-#ifndef MANET_REFINE_DENSE_LANES
-#define MANET_REFINE_DENSE_LANES 16
-#endif
-constexpr int REFINE_DENSE_LANES = MANET_REFINE_DENSE_LANES;  // (64: off; smooth embeddings at cfg2 size: filter 0.66 -> 0.56 ms)
-#ifndef MANET_REFINE_RZ
-#define MANET_REFINE_RZ 4
-#endif
-constexpr int REFINE_RZ = MANET_REFINE_RZ;  // workgroups of the re-rank launch per bucket: each takes every 4th entry (the longest bucket is the launch's time)
+constexpr int REFINE_DENSE_MIN = 64;
+constexpr int REFINE_DENSE_LANES = 16;  // (64: off; smooth embeddings at cfg2 size: filter 0.66 -> 0.56 ms)
+constexpr int REFINE_RZ = 4;  // workgroups of the re-rank launch per bucket: each takes every 4th entry (the longest bucket is the launch's time)
 constexpr int ONE_ROUND_OK = 1 << 29;   // block_map flag (fp32 pipe kernel): the device may swap the host's splits for ONE round of long ones
 constexpr int RESCUE_LISTED = 1 << 30;  // block_map flag of the rescue launch: deal the workgroups to the LISTED tiles
 // block_map word: bits 0-7 tuning, bits 8-20 small_S (<= 4096: 13 bits) -- or, in the rescue launch, bits 8-28 its split count --
@@ -582,16 +556,12 @@ struct FramePrep {
     int emb_out_bf16, relu;
     int vec2;   // s_x == 1, even w / strides, aligned base: two pixels per load
     int rcopy;  // fp32 source + MANET_COMPUTE_BF16: LDS also holds a bf16-rounded copy
-    int abl;  // -DMANET_ABLATION builds, timing experiments: 1 no loads, 2 no plane stores, 4 no image stores, 8 no norm chain, 16 no data blocks, 32 no aux blocks
+    int abl;    // always 0 (kept: the hot kernel's argument block stays as measured)
 };
-#ifdef MANET_ABLATION
-#define MANET_FP_ABL(bit_) (A.abl & (bit_))
-#else
-#define MANET_FP_ABL(bit_) false
-#endif
 // VEC2 (r6): the two staging forms are separate instantiations -- as a run-time branch (r3-r5) both lived in every kernel and the
 // 2-byte instantiation ran out of scalar registers (22 SGPR spills and a 36-byte private segment; tests/test_kernel_resources.py)
-template <typename SRC, int XC, bool VEC2>
+constexpr int XC = 32;  // full-resolution columns per workgroup
+template <typename SRC, bool VEC2>
 __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
 {
     constexpr int PIX = 2 * XC;
@@ -601,8 +571,6 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
     char *ws = A.ws + (long)blockIdx.z * A.ws_stride;
     float *plane = (float *)(ws + A.off_plane);
     const int C = A.C, kpad = A.kpad, units = A.units;
-    if (MANET_FP_ABL(16) && (int)blockIdx.x < A.n_data) return;
-    if (MANET_FP_ABL(32) && (int)blockIdx.x >= A.n_data) return;
     if ((int)blockIdx.x >= A.n_data) {  // ---- auxiliary blocks
         const long gid = (long)(blockIdx.x - A.n_data) * 256 + tid, gstride = (long)(gridDim.x - A.n_data) * 256;
         if (A.d >= 0) {
@@ -668,8 +636,7 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
         const int p = 2 * pp, y = y0 + p / XC, x = x0 + p % XC;  // (XC is even: both pixels in one row; w is even)
         const bool in = (y < A.h && x < A.w);
         const SRC *sp = src + (long)(y < A.h ? y : A.h - 1) * A.s_y + (long)(x < A.w ? x : A.w - 2);
-        long sc_ = A.s_c;
-        if (MANET_FP_ABL(1)) { sp = src; sc_ = 0; }  // (timing ablation: every load hits one cached line)
+        const long sc_ = A.s_c;
         float *r0 = rows + p * KP, *q0 = rq + p * KP;
         auto stage2 = [&](auto kb_tag) __attribute__((always_inline)) {
             constexpr int KB = decltype(kb_tag)::value;
@@ -724,8 +691,7 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
         const int y = y0 + p / XC, x = x0 + p % XC;
         const bool in = (y < A.h && x < A.w);
         const SRC *sp = src + (long)(y < A.h ? y : A.h - 1) * A.s_y + (long)(x < A.w ? x : A.w - 1) * A.s_x;
-        long sc_ = A.s_c;
-        if (MANET_FP_ABL(1)) { sp = src; sc_ = 0; }
+        const long sc_ = A.s_c;
         float *rp_ = rows + p * KP, *qp_ = rq + p * KP;
         auto stage = [&](auto kb_tag) __attribute__((always_inline)) {
             constexpr int KB = decltype(kb_tag)::value;
@@ -793,13 +759,13 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
     };
     // (f32 image: the last units / 6 units of every pixel are wave 0's as well -- its share of the store work behind the chain)
     const int u_split = f32img ? units - units / 6 : units;
-    if (tid < PIX) {  // ---- wave 0 (PIX = 64 lanes; XC = 64 builds: two waves)
+    if (tid < PIX) {  // ---- wave 0 (PIX = 64 lanes)
         const int p = tid;
         const int y = y0 + p / XC, x = x0 + p % XC;
         const bool in = (y < A.h && x < A.w);
         const long n = (long)y * A.w + x;
         float nrm = 0.0f;
-        if (!MANET_FP_ABL(8)) {  // |q|^2: the k-ascending fmaf chain of the oracle, as pack_rows_kernel (reads batched ahead)
+        {  // |q|^2: the k-ascending fmaf chain of the oracle, as pack_rows_kernel (reads batched ahead)
             const float *row = (A.compute == MANET_COMPUTE_BF16 ? rq : rows) + p * KP;
             const bool rnd = (A.compute == MANET_COMPUTE_BF16) && !bf16_exact;
             int k = 0;
@@ -818,7 +784,7 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
                 nrm = fmaf(xv, xv, nrm);
             }
         }
-        if (in && !MANET_FP_ABL(4)) {
+        if (in) {
             if (f32img) {
                 *(float *)(ws + (n >> 5) * A.qblk_bytes + (long)units * QB * 16 + (n & 31) * 4) = nrm;
                 for (int u = u_split; u < units; ++u) *(f32x4 *)image_addr(n, u) = image_unit_f32(rows + p * KP, u);
@@ -831,7 +797,7 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
     if (tid >= PIX) {  // ---- the other waves
         const int t = tid - PIX, NT = 256 - PIX;
         // pooled plane row d + rp (IntVOS.py:282-284: window summed row-major, times 1/4)
-        if (A.d >= 0 && rp < A.hp && !MANET_FP_ABL(2)) {
+        if (A.d >= 0 && rp < A.hp) {
             float *prow = plane + (long)(A.d + rp) * A.WS + A.d + x0 / 2;
             for (int idx = t; idx < (XC / 2) * C; idx += NT) {
                 const int c = idx / (XC / 2), px = idx - c * (XC / 2);
@@ -842,17 +808,15 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
             }
         }
         // operand image: pixel (y, x) is query row n = y w + x -> block n / 32, row n % 32
-        if (!MANET_FP_ABL(4)) {
-            for (int item = t; item < u_split * PIX; item += NT) {
-                const int p = item % PIX, u = item / PIX;
-                const int y = y0 + p / XC, x = x0 + p % XC;
-                if (y >= A.h || x >= A.w) continue;
-                const long n = (long)y * A.w + x;
-                if (f32img) *(f32x4 *)image_addr(n, u) = image_unit_f32(rows + p * KP, u);
-                else if (unit_is_special(u)) continue;  // (wave 0, behind the norm chain)
-                else if (bf16_exact) *(uint4 *)image_addr(n, u) = unit_bf16_exact(rq + p * KP, u);
-                else *(uint4 *)image_addr(n, u) = image_unit_bf16<true>(rows + p * KP, u, hi_units, C, 0.0f);
-            }
+        for (int item = t; item < u_split * PIX; item += NT) {
+            const int p = item % PIX, u = item / PIX;
+            const int y = y0 + p / XC, x = x0 + p % XC;
+            if (y >= A.h || x >= A.w) continue;
+            const long n = (long)y * A.w + x;
+            if (f32img) *(f32x4 *)image_addr(n, u) = image_unit_f32(rows + p * KP, u);
+            else if (unit_is_special(u)) continue;  // (wave 0, behind the norm chain)
+            else if (bf16_exact) *(uint4 *)image_addr(n, u) = unit_bf16_exact(rq + p * KP, u);
+            else *(uint4 *)image_addr(n, u) = image_unit_bf16<true>(rows + p * KP, u, hi_units, C, 0.0f);
         }
     }
 }
@@ -906,10 +870,7 @@ __device__ __forceinline__ float min3p(float m, float a, float b)
 // block -> (tile, split) map (such a bank fits every XCD's L2 anyway).  The minimum is order-independent: same bits.
 // `block_map`: bits 0-7 = tuning (0: XCD-aware, 1: tile fastest, 2: split fastest, 4..7: XCD-aware with 2..5 splits
 // fastest), bits 8.. = small_S.
-#ifndef MANET_FILTER_TAIL_CUTS
-#define MANET_FILTER_TAIL_CUTS 4
-#endif
-constexpr int FILTER_TAIL_CUTS = MANET_FILTER_TAIL_CUTS;  // (1: bm == 3's map)
+constexpr int FILTER_TAIL_CUTS = 4;  // (1: bm == 3's map)
 __device__ __forceinline__ bool split_of_block(int b, int nQT, int S, int T, int block_map, int &qt, int &s, int &t0,
                                                int &t1)
 {
@@ -1292,7 +1253,7 @@ __global__ __launch_bounds__(256, 2) void global_match_f32_pipe_kernel(const cha
         // splits per tile: whole rounds of the chip's 512 workgroup slots (a workgroup's fixed cost -- its 106 KB query
         // operand, the pipeline fill, the closing atomics -- is worth ~6 tiles of matrix work: few long workgroups beat many
         // short ones; 4 tiles of 102 at cfg2 size: 390 us with 404 splits of 5 tiles, 3.2 rounds)
-        int Sd = (block_map >> 8) & BLOCK_MAP_RESCUE_MASK;  // (experiments: MANET_TUNE_RESCUE_SPLITS)
+        int Sd = (block_map >> 8) & BLOCK_MAP_RESCUE_MASK;  // (a forced count; the shipped launch passes 0: the choice below)
         if (Sd > 0) {
             const int most_grid = (int)gridDim.x / nr;
             Sd = Sd > most_grid ? most_grid : Sd;
@@ -1469,36 +1430,32 @@ __global__ __launch_bounds__(256, 2) void global_match_f32_pipe_kernel(const cha
 }
 
 // ---------------------------------------------------------------------------------------------
-// main kernel, bf16 operands (MANET_COMPUTE_BF16 / _BF16X3): one workgroup = 512 queries x one bank
+// main kernel, split-bf16 operands (MANET_COMPUTE_BF16X3): one workgroup = 512 queries x one bank
 // split, 8 waves.  Same decomposition as the f32 kernel (swapped operands, object-pure 64-row tiles,
 // lane-local running min, atomicMin across splits); the contraction is v_mfma_f32_32x32x16_bf16 with fp32
-// accumulation:
-//   X3 = false: one MFMA per 16 k on embeddings rounded to bf16 (7 instead of 50 MFMAs per block at C=100)
-//   X3 = true : hi*hi + hi*lo + lo*hi with x = hi + lo, hi = bf16(x), lo = bf16(x - hi): the dropped
-//               lo*lo term is <= 2^-16 relative, i.e. fp32-class distances at 3/16 of the f32 MFMA cost.
+// accumulation of hi*hi + hi*lo + lo*hi with x = hi + lo, hi = bf16(x), lo = bf16(x - hi): the dropped
+// lo*lo term is <= 2^-16 relative, i.e. fp32-class distances at 3/16 of the f32 MFMA cost.
 // The operand images carry -2q and both squared norms (see Geom), so an accumulator element IS
 // d(n, m) = |q|^2 + |k|^2 - 2 q.k when the k loop ends: the epilogue is ONE v_minimum3_f32 per two
 // elements (r1: add + fma + min per element = 6x the VALU work, 0.32 of 0.68 ms).
-// Staging: TPS tiles per step, double buffered in LDS; DMA = true: asm LDS-DMA (no VGPR round trip, no
-// ds_write pass, the loads of step s+1 fly during the whole of step s); DMA = false: r1's register staging.
-template <int KSB, bool X3, int TPS, bool DMA>
-__global__ __launch_bounds__(512, 1) void global_match_bf16_kernel(const char *__restrict__ qpack,
-                                                                   const char *__restrict__ bpack,
-                                                                   const int *__restrict__ meta, int n_ids,
-                                                                   int nQT, int S, long N_pad,
-                                                                   unsigned *__restrict__ keys, int block_map,
-                                                                   int young_prio)
+// Staging: one tile per step, double buffered in LDS by asm LDS-DMA (no VGPR round trip, no ds_write pass,
+// the loads of step s+1 fly during the whole of step s).
+template <int KSB>
+__global__ __launch_bounds__(512, 1) void global_match_bf16x3_kernel(const char *__restrict__ qpack,
+                                                                     const char *__restrict__ bpack,
+                                                                     const int *__restrict__ meta, int n_ids,
+                                                                     int nQT, int S, long N_pad,
+                                                                     unsigned *__restrict__ keys, int block_map)
 {
     typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
     constexpr int NW = 8;
-    constexpr int UNITS = 2 * KSB * (X3 ? 2 : 1);
+    constexpr int UNITS = 4 * KSB;
     constexpr int LO = 2 * KSB;  // first unit of the lo image
     constexpr size_t TILE_BYTES = bank_tile_bytes_u(UNITS, false);  // = UNITS KiB
     constexpr size_t QBLK_BYTES = query_block_bytes_u(UNITS, false);
-    constexpr size_t STEP_BYTES = TILE_BYTES * TPS;
     constexpr int QTB = NW * 64;
     static_assert(TILE_BYTES == (size_t)UNITS * 1024, "a bf16 tile is a whole number of 1 KiB DMA pieces");
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 x STEP_BYTES
+    extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 x TILE_BYTES
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1510,43 +1467,22 @@ __global__ __launch_bounds__(512, 1) void global_match_bf16_kernel(const char *_
     const int T = meta[META_T];
     if (!split_of_block(blockIdx.x, nQT, S, T, block_map, qt, s, t0, t1)) return;
 
-    // ---- staging of one STEP = TPS consecutive tiles ------------------------------------------------
-    constexpr int PIECES = UNITS * TPS;  // 1 KiB pieces per step
+    // ---- staging of one tile: UNITS 1 KiB pieces, dealt to the waves ---------------------------------
     const unsigned smem_base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)smem);
     auto stage_dma = [&](int t, int slot) __attribute__((always_inline)) {
-        const int np = ((t1 - t) < TPS ? (t1 - t) : TPS) * UNITS;  // the split's last step may be short
+        const int np = ((t1 - t) < 1 ? (t1 - t) : 1) * UNITS;  // (<= 0 behind the split's end: nothing staged)
         const char *g = bpack + (size_t)t * TILE_BYTES + (size_t)lane * 16;
-        const unsigned l = smem_base + (unsigned)slot * (unsigned)STEP_BYTES;
+        const unsigned l = smem_base + (unsigned)slot * (unsigned)TILE_BYTES;
 #pragma unroll
-        for (int i = 0; i < (PIECES + NW - 1) / NW; ++i) {
+        for (int i = 0; i < (UNITS + NW - 1) / NW; ++i) {
             const int pc = wave + i * NW;  // wave-uniform
             if (pc < np) lds_dma16(g + (size_t)pc * 1024, l + (unsigned)pc * 1024u);
         }
     };
-    constexpr int NV = (int)(TILE_BYTES / 16) * TPS;
-    constexpr int NLD = DMA ? 1 : (NV + NW * 64 - 1) / (NW * 64);
-    constexpr int NTHR = NW * 64;
-    u32x4 Ra[NLD];
-    auto gload = [&](int t) __attribute__((always_inline)) {
-        const u32x4 *g_ = (const u32x4 *)(bpack + (size_t)t * TILE_BYTES);
-        const int lim_ = ((t1 - t) < TPS ? (t1 - t) : TPS) * (int)(TILE_BYTES / 16);
-#pragma unroll
-        for (int i_ = 0; i_ < NLD; ++i_) {
-            const int idx_ = i_ * NTHR + tid;
-            Ra[i_] = g_[idx_ < lim_ ? idx_ : lim_ - 1];  // clamped into the split's own range
-        }
-    };
-    auto lstore = [&](int slot) __attribute__((always_inline)) {
-        u32x4 *l_ = (u32x4 *)(smem + (size_t)slot * STEP_BYTES);
-#pragma unroll
-        for (int i_ = 0; i_ < NLD; ++i_)
-            if (i_ * NTHR + tid < NV) l_[i_ * NTHR + tid] = Ra[i_];
-    };
-    if (DMA) stage_dma(t0, 0);
-    else gload(t0);
+    stage_dma(t0, 0);
 
-    // B operand: lane holds (-2q | norm slots)[j = lane&31][k = 16s + 8*(lane>>5) + 0..7] for its two blocks
-    u32x4 q0[KSB], q1[KSB], q0l[X3 ? KSB : 1], q1l[X3 ? KSB : 1];
+    // B operand: lane holds (-2q | norm slots)[j = lane&31][k = 16s + 8*(lane>>5) + 0..7] for its two blocks, hi and lo image
+    u32x4 q0[KSB], q1[KSB], q0l[KSB], q1l[KSB];
     {
         const char *qb0 = qpack + (size_t)(qt * (QTB / QB) + wave * 2) * QBLK_BYTES;
         const char *qb1 = qb0 + QBLK_BYTES;
@@ -1554,10 +1490,8 @@ __global__ __launch_bounds__(512, 1) void global_match_bf16_kernel(const char *_
         for (int k = 0; k < KSB; ++k) {
             q0[k] = *(const u32x4 *)(qb0 + ((size_t)(k * 2 + h) * QB + l31) * 16);
             q1[k] = *(const u32x4 *)(qb1 + ((size_t)(k * 2 + h) * QB + l31) * 16);
-            if (X3) {
-                q0l[k] = *(const u32x4 *)(qb0 + ((size_t)(LO + k * 2 + h) * QB + l31) * 16);
-                q1l[k] = *(const u32x4 *)(qb1 + ((size_t)(LO + k * 2 + h) * QB + l31) * 16);
-            }
+            q0l[k] = *(const u32x4 *)(qb0 + ((size_t)(LO + k * 2 + h) * QB + l31) * 16);
+            q1l[k] = *(const u32x4 *)(qb1 + ((size_t)(LO + k * 2 + h) * QB + l31) * 16);
         }
     }
     const long qbase = (long)qt * QTB + wave * 64 + l31;
@@ -1567,7 +1501,7 @@ __global__ __launch_bounds__(512, 1) void global_match_bf16_kernel(const char *_
 #pragma unroll
     for (int k = 0; k < KSB; ++k) {
         asm volatile("" : "+v"(q0[k]), "+v"(q1[k]));
-        if (X3) asm volatile("" : "+v"(q0l[k]), "+v"(q1l[k]));
+        asm volatile("" : "+v"(q0l[k]), "+v"(q1l[k]));
     }
 
     int o = 0;
@@ -1586,46 +1520,28 @@ __global__ __launch_bounds__(512, 1) void global_match_bf16_kernel(const char *_
     };
 #define MANET_BF(x) __builtin_bit_cast(bf16x8_t, x)
 #define MANET_MFMA(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(MANET_BF(a_), MANET_BF(b_), c_, 0, 0, 0)
-    // one 64-row tile: 4 x KSB (x3) MFMAs from zero accumulators, then the running minimum
+    // one 64-row tile: 12 x KSB MFMAs from zero accumulators, then the running minimum
     auto tile = [&](const char *tb) __attribute__((always_inline)) {
         const u32x4 *A = (const u32x4 *)tb;
         f32x16 c00 = {0}, c01 = {0}, c10 = {0}, c11 = {0};
-        if (!X3) {
-            // all A fragments of the tile first (2 x KSB ds_read_b128 in flight), then the MFMAs back to
-            // back behind counted lgkmcnt waits: the matrix pipe never waits for an LDS round trip
-            u32x4 a0[KSB], a1[KSB];
 #pragma unroll
-            for (int k = 0; k < KSB; ++k) {
-                a0[k] = A[(k * 2 + h) * BT + l31];
-                a1[k] = A[(k * 2 + h) * BT + 32 + l31];
-            }
-#pragma unroll
-            for (int k = 0; k < KSB; ++k) {
-                MANET_MFMA(a0[k], q0[k], c00);
-                MANET_MFMA(a1[k], q0[k], c10);
-                MANET_MFMA(a0[k], q1[k], c01);
-                MANET_MFMA(a1[k], q1[k], c11);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < KSB; ++k) {
-                u32x4 a0 = A[(k * 2 + h) * BT + l31];
-                u32x4 a1 = A[(k * 2 + h) * BT + 32 + l31];
-                u32x4 a0l = A[(LO + k * 2 + h) * BT + l31];
-                u32x4 a1l = A[(LO + k * 2 + h) * BT + 32 + l31];
-                MANET_MFMA(a0, q0[k], c00);
-                MANET_MFMA(a1, q0[k], c10);
-                MANET_MFMA(a0, q1[k], c01);
-                MANET_MFMA(a1, q1[k], c11);
-                MANET_MFMA(a0, q0l[k], c00);
-                MANET_MFMA(a1, q0l[k], c10);
-                MANET_MFMA(a0, q1l[k], c01);
-                MANET_MFMA(a1, q1l[k], c11);
-                MANET_MFMA(a0l, q0[k], c00);
-                MANET_MFMA(a1l, q0[k], c10);
-                MANET_MFMA(a0l, q1[k], c01);
-                MANET_MFMA(a1l, q1[k], c11);
-            }
+        for (int k = 0; k < KSB; ++k) {
+            u32x4 a0 = A[(k * 2 + h) * BT + l31];
+            u32x4 a1 = A[(k * 2 + h) * BT + 32 + l31];
+            u32x4 a0l = A[(LO + k * 2 + h) * BT + l31];
+            u32x4 a1l = A[(LO + k * 2 + h) * BT + 32 + l31];
+            MANET_MFMA(a0, q0[k], c00);
+            MANET_MFMA(a1, q0[k], c10);
+            MANET_MFMA(a0, q1[k], c01);
+            MANET_MFMA(a1, q1[k], c11);
+            MANET_MFMA(a0, q0l[k], c00);
+            MANET_MFMA(a1, q0l[k], c10);
+            MANET_MFMA(a0, q1l[k], c01);
+            MANET_MFMA(a1, q1l[k], c11);
+            MANET_MFMA(a0l, q0[k], c00);
+            MANET_MFMA(a1l, q0[k], c10);
+            MANET_MFMA(a0l, q1[k], c01);
+            MANET_MFMA(a1l, q1[k], c11);
         }
         // accumulator register r of block rb = bank row rb*32 + (r&3) + 8*(r>>2) + 4*h; all of them belong
         // to the same object, so the reduction over rows is register-wise
@@ -1644,37 +1560,16 @@ __global__ __launch_bounds__(512, 1) void global_match_bf16_kernel(const char *_
             do { ++o; seg_end = meta[META_SEG + o + 1]; } while (t >= seg_end);
         }
     };
-    // static priority for the younger half of the workgroup (waves 4-7 lose every VALU arbitration against
-    // their SIMD partner otherwise; MI355X_MICROARCH.md "two waves per SIMD", item 4)
-    if (young_prio && wave >= 4) __builtin_amdgcn_s_setprio(1);
-
-    if (!DMA) {
-        lstore(0);
-        if (t0 + TPS < t1) gload(t0 + TPS);
-    }
     int buf = 0;
-    for (int t = t0; t < t1; t += TPS, buf ^= 1) {
-        if (DMA) {
-            // this wave's pieces of the step have landed; the barrier then publishes everybody's pieces
-            // and tells us that every wave is done reading the other buffer (the previous step)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (t + TPS < t1) stage_dma(t + TPS, buf ^ 1);  // in flight during the whole step
-        } else {
-            __syncthreads();  // step's tiles visible in `buf`; the other buffer is free
-            if (t + TPS < t1) {
-                lstore(buf ^ 1);
-                if (t + 2 * TPS < t1) gload(t + 2 * TPS);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < TPS; ++u) {
-            if (t + u < t1) {
-                next_object(t + u);
-                tile(smem + (size_t)buf * STEP_BYTES + (size_t)u * TILE_BYTES);
-            }
-        }
+    for (int t = t0; t < t1; ++t, buf ^= 1) {
+        // this wave's pieces of the tile have landed; the barrier then publishes everybody's pieces
+        // and tells us that every wave is done reading the other buffer (the previous tile)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (t + 1 < t1) stage_dma(t + 1, buf ^ 1);  // in flight during the whole step
+        next_object(t);
+        tile(smem + (size_t)buf * TILE_BYTES);
     }
 #undef MANET_MFMA
 #undef MANET_BF
@@ -1683,7 +1578,8 @@ __global__ __launch_bounds__(512, 1) void global_match_bf16_kernel(const char *_
 
 // ---------------------------------------------------------------------------------------------
 // Software-pipelined form of the plain-bf16 kernel (the shipped one for MANET_COMPUTE_BF16).
-// Same decomposition and arithmetic as global_match_bf16_kernel<KSB, false, 2, true>; what changes is WHEN
+// Same decomposition as global_match_bf16x3_kernel, one MFMA per 16 k on embeddings rounded to bf16 (7 instead of
+// 50 MFMAs per block at C = 100) and two tiles per step; what differs is WHEN
 // things are issued, so that the matrix pipe never waits for LDS (r2 PMC of the kernel above: pipe 67 %
 // busy, waves parked 37 % of their cycles on s_waitcnt -- the A-fragment reads right behind every barrier):
 //   * a step = 2 tiles (A, B); fragment registers F[k] are bound to k-step k: as soon as the four MFMAs of
@@ -1693,14 +1589,13 @@ __global__ __launch_bounds__(512, 1) void global_match_bf16_kernel(const char *_
 //     registers, so the barrier (a) publishes the next step's buffer, whose first fragments tile B's k-steps
 //     prefetch, and (b) frees the current buffer for the LDS-DMA of the step after next.  No fragment read
 //     ever follows a barrier directly; two LDS buffers suffice.
-// ABL: timing ablations only (results are garbage): 1 = no DMA / no vmcnt wait, 2 = no barrier, 4 = epilogue
-// reduced to one min3, 8 = no fragment refills.  (A 3-deep LDS ring with counted vmcnt(N) waits -- the DMA two
-// steps ahead -- was measured slower, 0.529 vs 0.498 ms, and removed: DMA latency is not the stall.)
-template <int KSB, int ABL>
+// (A 3-deep LDS ring with counted vmcnt(N) waits -- the DMA two steps ahead -- was measured slower, 0.529 vs
+// 0.498 ms, and removed: DMA latency is not the stall.)
+template <int KSB>
 __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *__restrict__ bpack,
                                    const int *__restrict__ meta, int n_ids, int nQT, int S, long N_pad,
-                                   unsigned *__restrict__ keys, int block_map, int young_prio)
+                                   unsigned *__restrict__ keys, int block_map)
 {
     typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
     constexpr int NW = 8, TPS = 2;
@@ -1724,8 +1619,7 @@ void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *_
 
     constexpr int PIECES = UNITS * TPS;  // 1 KiB pieces per step
     const unsigned smem_base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)smem);
-    auto stage_dma = [&](int t, int slot, bool prologue = false) __attribute__((always_inline)) {
-        if ((ABL & 1) && !prologue) return;  // ablation: only the first steps are staged (real data in LDS)
+    auto stage_dma = [&](int t, int slot) __attribute__((always_inline)) {
         const int np = ((t1 - t) < TPS ? (t1 - t) : TPS) * UNITS;  // the split's last step may be short
         const char *g = bpack + (size_t)t * TILE_BYTES + (size_t)lane * 16;
         const unsigned l = smem_base + (unsigned)slot * (unsigned)STEP_BYTES;
@@ -1735,8 +1629,8 @@ void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *_
             if (pc < np) lds_dma16(g + (size_t)pc * 1024, l + (unsigned)pc * 1024u);
         }
     };
-    stage_dma(t0, 0, true);
-    if (t0 + TPS < t1) stage_dma(t0 + TPS, 1, true);
+    stage_dma(t0, 0);
+    if (t0 + TPS < t1) stage_dma(t0 + TPS, 1);
 
     u32x4 q0[KSB], q1[KSB];
     {
@@ -1772,8 +1666,6 @@ void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *_
             do { ++o; seg_end = meta[META_SEG + o + 1]; } while (t >= seg_end);
         }
     };
-    if (young_prio && wave >= 4) __builtin_amdgcn_s_setprio(1);
-
     // this lane's fragment offset inside a tile image: unit (2k + h), rows l31 and 32 + l31
     const unsigned frag_off = (unsigned)((h * BT + l31) * 16);
     u32x4 F0[KSB], F1[KSB];
@@ -1795,11 +1687,11 @@ void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *_
             MANET_MFMA(F1[k], q0[k], c10);                                                         \
             MANET_MFMA(F0[k], q1[k], c01);                                                         \
             MANET_MFMA(F1[k], q1[k], c11);                                                         \
-            if (!(ABL & 8)) MANET_LOADF(k, next_base_);                                            \
+            MANET_LOADF(k, next_base_);                                                            \
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); /* 4 MFMA  */                       \
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); /* 2 DS read: the refill, right behind them */ \
         }                                                                                          \
-        _Pragma("unroll") for (int r = 0; r < ((ABL & 4) ? 2 : 16); r += 2)                        \
+        _Pragma("unroll") for (int r = 0; r < 16; r += 2)                                          \
         {                                                                                          \
             m0a = min3p(m0a, c00[r], c10[r]);                                                      \
             m0b = min3p(m0b, c00[r + 1], c10[r + 1]);                                              \
@@ -1825,9 +1717,9 @@ void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *_
         // ---- mid-step: everything of this buffer is in registers now.  This wave's pieces of the next step have
         // landed (issued one step ago); the barrier publishes the next step's buffer and frees this one for the
         // step after next.
-        if (!(ABL & 1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of `cur` have returned
-        if (!(ABL & 2)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (t + NBUF * TPS < t1) stage_dma(t + NBUF * TPS, buf);
         // ---- tile B (refill F with tile A of the next step's buffer; a stale read if there is none)
@@ -1858,13 +1750,13 @@ void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *_
 // fill count; an entry that does not fit raises stats[1]).  A pass's 16 distances per lane are first reduced to their minimum --
 // the same eight v_minimum3 the plain kernel spends -- and only a wave in which some lane's minimum passes its threshold
 // takes the slow path that looks at the individual rows.
-template <int KSB, int ABL, bool FILTER = false>
+template <int KSB, bool FILTER = false>
 __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const char *__restrict__ qpack,
                                                                         const char *__restrict__ bpack,
                                                                         const int *__restrict__ meta, int n_ids,
                                                                         int nQT, int S, long N_pad,
                                                                         unsigned *__restrict__ keys, int block_map,
-                                                                        int young_prio, unsigned *__restrict__ thr,
+                                                                        unsigned *__restrict__ thr,
                                                                         const float *__restrict__ slack,
                                                                         unsigned long long *__restrict__ stats,
                                                                         uint2 *__restrict__ list, long bucket_cap,
@@ -1895,8 +1787,7 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
 
     constexpr int PIECES = UNITS * TPS;  // 1 KiB pieces per step
     const unsigned smem_base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)smem);
-    auto stage_dma = [&](int t, int slot, bool prologue = false) __attribute__((always_inline)) {
-        if ((ABL & 1) && !prologue) return;
+    auto stage_dma = [&](int t, int slot) __attribute__((always_inline)) {
         const int np = ((t1 - t) < TPS ? (t1 - t) : TPS) * UNITS;  // the split's last step may be short
         const unsigned l = smem_base + (unsigned)slot * (unsigned)STEP_BYTES;
         if (FILTER) {  // (at the register limit: a uniform base + this lane's 32-bit offset, no 64-bit address pair)
@@ -1915,8 +1806,8 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
             if (pc < np) lds_dma16(g + (size_t)pc * 1024, l + (unsigned)pc * 1024u);
         }
     };
-    stage_dma(t0, 0, true);
-    if (t0 + TPS < t1) stage_dma(t0 + TPS, 1, true);
+    stage_dma(t0, 0);
+    if (t0 + TPS < t1) stage_dma(t0 + TPS, 1);
 
     u32x4 q[NQB][KSB];
     {
@@ -1980,7 +1871,6 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
             if (h == 0) atomicMin(&(keys + (size_t)obj * N_pad)[qbase + 32u * j], key_of(a));
         }
     };
-    (void)young_prio;
     // FILTER: minimum of a pass's 16 distances of one query block, and the slow path that appends the qualifying rows
     // (accumulator register r of lane (l31, h) is bank row (r & 3) + 8 (r >> 2) + 4 h of the pass)
     auto min16 = [&](const f32x16 &c) __attribute__((always_inline)) {
@@ -2012,7 +1902,6 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
         asm volatile("" : "+s"(b32), "+s"(sub_off));
         const long b = (long)b32;
         unsigned base = 0u;
-        if (!(ABL & 64))
         if (lane == 0) base = atomicAdd(&bcnt[b], (unsigned)cnt) & 0x7fffffffu;  // (bit 31 = the bucket's "incomplete" mark)
         base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
         uint2 *dst = list + b * bucket_cap + base;  // (wave-uniform)
@@ -2027,10 +1916,6 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
         wl_total += cnt;
     };
     auto emit_regs = [&](const f32x16 &c, float t, int j, int row0) __attribute__((always_inline)) {
-        if (ABL & 128) {  // (timing: the tests without the listing)
-            wl_n[j] += (int)(__popcll(__ballot(c[0] <= t)) & 1);
-            return;
-        }
         const unsigned lq = (unsigned)(wave * (NQB * QB) + l31 + 32 * j);  // query inside the workgroup's 512
         // (four registers at a time first: a block usually has its one or two hits in one group -- 8 tests instead of 16)
 #pragma unroll
@@ -2104,12 +1989,11 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
             MANET_MFMA(F[k], q[1][k], c1);                                                         \
             MANET_MFMA(F[k], q[2][k], c2);                                                         \
             MANET_MFMA(F[k], q[3][k], c3);                                                         \
-            if (!(ABL & 8)) MANET_LOADF(k, next_base_);                                            \
+            MANET_LOADF(k, next_base_);                                                            \
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); /* 4 MFMA */                        \
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); /* the refill right behind them */  \
         }                                                                                          \
-        {                                                                                          \
-        _Pragma("unroll") for (int r = 0; r < ((ABL & 4) ? 2 : 16); r += 4)                        \
+        _Pragma("unroll") for (int r = 0; r < 16; r += 4)                                          \
         {                                                                                          \
             ma[0] = min3p(ma[0], c0[r], c0[r + 2]);                                                \
             mb[0] = min3p(mb[0], c0[r + 1], c0[r + 3]);                                            \
@@ -2119,7 +2003,6 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
             mb[2] = min3p(mb[2], c2[r + 1], c2[r + 3]);                                            \
             ma[3] = min3p(ma[3], c3[r], c3[r + 2]);                                                \
             mb[3] = min3p(mb[3], c3[r + 1], c3[r + 3]);                                            \
-        }                                                                                          \
         }                                                                                          \
     }
 
@@ -2137,15 +2020,10 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
         tq[ja_] = fminf(tq[ja_], pa + sq[ja_]);                                                    \
         tq[jb_] = fminf(tq[jb_], pb + sq[jb_]);                                                    \
         const bool ha = pa <= tq[ja_], hb = pb <= tq[jb_];                                         \
-        if (!(ABL & 16) && __ballot(ha | hb)) { /* wave-uniform */                                 \
-            const unsigned long long tk0_ = (ABL & 256) ? __builtin_readcyclecounter() : 0ull;     \
+        if (__ballot(ha | hb)) { /* wave-uniform */                                                \
             const unsigned long long ma_ = __ballot(ha), mb_ = __ballot(hb);                       \
             if (ma_) emit(ca_, tq[ja_], ja_, (row0_), ma_);                                        \
             if (mb_) emit(cb_, tq[jb_], jb_, (row0_), mb_);                                        \
-            if (ABL & 256) {                                                                       \
-                dbg_cycles += __builtin_readcyclecounter() - tk0_;                                 \
-                dbg_events += 1;                                                                   \
-            }                                                                                      \
         }                                                                                          \
     }
 #define MANET_PASS_F(next_base_, row0_)                                                            \
@@ -2173,8 +2051,6 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
         MANET_TEST2(c0, c1, 0, 1, (row0_));                                                        \
         pend_row0 = (row0_);                                                                       \
     }
-    unsigned long long dbg_cycles = 0ull, dbg_events = 0ull;  // (ABL & 256: cycles this wave spent behind the tests, and how often)
-    const unsigned long long dbg_t0 = (ABL & 256) ? __builtin_readcyclecounter() : 0ull;
     unsigned xk[NQB] = {0u, 0u, 0u, 0u};  // FILTER: threshold keys asked for in the previous exchange step, of object xo
     int xo = -1;
     f32x16 pc2, pc3;  // FILTER: the pending half (nothing pending: distances no threshold admits)
@@ -2232,9 +2108,9 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
         }
         // ---- this wave's pieces of the next step have landed (issued one step ago) and its reads of `cur`
         // have returned; the barrier publishes the next buffer and frees `cur` for step + 2
-        if (!(ABL & 1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (!(ABL & 2)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (FILTER) {
             // threshold exchange with the workgroups running beside this one on the same queries and object: every fourth
@@ -2249,7 +2125,7 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
                 }
             }
             xo = -1;
-            if (!(ABL & 32) && (((t - t0) / TPS) & REFINE_XCHG_MASK) == REFINE_XCHG_MASK) {
+            if ((((t - t0) / TPS) & REFINE_XCHG_MASK) == REFINE_XCHG_MASK) {
                 flush(o);
                 xo = o;
 #pragma unroll
@@ -2281,14 +2157,6 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
 #pragma unroll
         for (int j = 0; j < NQB; ++j) flush_sub(j);
         if (lane == 0 && wl_total) atomicAdd(&stats[0], (unsigned long long)wl_total);  // (statistics only)
-        if ((ABL & 256) && lane == 0) {  // timing experiments: stats[4..7] = listing cycles, listing events, wave cycles, waves
-            atomicAdd(&stats[4], dbg_cycles);
-            atomicAdd(&stats[5], dbg_events);
-            atomicAdd(&stats[6], __builtin_readcyclecounter() - dbg_t0);
-            atomicAdd(&stats[7], 1ull);
-            atomicMax(&stats[8], dbg_cycles);
-            atomicMax(&stats[9], __builtin_readcyclecounter() - dbg_t0);
-        }
     }
 }
 
@@ -2392,7 +2260,6 @@ __global__ void refine_threshold_kernel(const unsigned *__restrict__ keys, const
 {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) stats[0] = stats[1] = 0ull;
-    if (i >= 4 && i < 10) stats[i] = 0ull;  // (ablation builds: cycle counters of the filter pass)
     if (i <= 2 * (N_pad / QB)) bcnt[i] = 0u;  // (entries appended, dense entries appended, number of tiles to rescue)
     if (i >= (long)n_ids * N_pad) return;
     const long n = i % N_pad;
@@ -2437,16 +2304,6 @@ __global__ void refine_force_kernel(long N_pad, int n_ids, unsigned *__restrict_
     if (i == 0) bcnt[2 * (N_pad / QB)] = 0u;  // (the re-rank launch lists the tiles to rescue: all of them)
     if (i < (long)n_ids * N_pad) keys2[i] = 0xffffffffu;
 }
-
-#ifdef MANET_ABLATION
-// timing experiments (manet_tune_set(MANET_TUNE_ABLATION, 256)): what the filter pass's waves spent behind their threshold tests
-__global__ void refine_debug_kernel(const unsigned long long *stats)
-{
-    printf("filter pass: %llu waves, %.0f cycles each (longest %llu); listing path: %llu events, %.0f cycles each, %.1f %% of the wave "
-           "cycles (most in one wave: %llu cycles)\n", stats[7], (double)stats[6] / (double)(stats[7] ? stats[7] : 1), stats[9], stats[5],
-           (double)stats[4] / (double)(stats[5] ? stats[5] : 1), 100.0 * (double)stats[4] / (double)(stats[6] ? stats[6] : 1), stats[8]);
-}
-#endif
 
 // how many 256-query tiles of the last filter pass went through the rescue pass -> out2 = {rescued, tiles} (device memory: the
 // caller copies it out asynchronously and reads it a frame later)
@@ -2890,7 +2747,7 @@ void launch_rescue_f32_pipe(const char *qpack, const char *bpack, const int *met
     // matched: MANET_EPI_REFINE_EXACT) the fp32 kernel's own block map
     hipLaunchKernelGGL((global_match_f32_pipe_kernel<KS, true>), dim3((unsigned)(nQT * S)), dim3(256), lds, st, qpack, bpack, meta,
                        n_ids, nQT, S, N_pad, keys,
-                       listed ? (RESCUE_LISTED | ((manet_tune_get(MANET_TUNE_RESCUE_SPLITS, 0) & BLOCK_MAP_RESCUE_MASK) << 8)) : block_map_arg(nQT, 512, S),
+                       listed ? RESCUE_LISTED : block_map_arg(nQT, 512, S),
                        bcnt, bucket_cap);
 }
 
@@ -2908,98 +2765,37 @@ void launch_main_f32_pipe(const char *qpack, const char *bpack, const int *meta,
     manet_profile_record(st, false);
 }
 
-template <int KSB, bool X3, int TPS, bool DMA>
-void launch_main_bf16_v(const char *qpack, const char *bpack, const int *meta, int n_ids, int nQT, int S, long N_pad,
-                        unsigned *keys, int young_prio, hipStream_t st)
-{
-    size_t lds = 2 * TPS * bank_tile_bytes_u(2 * KSB * (X3 ? 2 : 1), false);
-    (void)hipFuncSetAttribute((const void *)global_match_bf16_kernel<KSB, X3, TPS, DMA>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    manet_profile_record(st, true);
-    hipLaunchKernelGGL((global_match_bf16_kernel<KSB, X3, TPS, DMA>), dim3((unsigned)(nQT * S)), dim3(512), lds, st,
-                       qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, block_map_arg(nQT, 256, S),
-                       young_prio);
-    manet_profile_record(st, false);
-}
-
-// Shipped: plain bf16 -> global_match_bf16_wide_kernel (global_match_bf16_pipe_kernel for C > 106);
-// split-bf16 -> global_match_bf16_kernel<KSB, true, 1, true> (1 tile per step, asm LDS-DMA staging).
-// MANET_TUNE_BF16_VARIANT (experiments; bit field, none of it changes a workspace layout):
-//   bits 0-1  global_match_bf16_kernel: tiles per step 0 = default, 1 = one, 2 = four (two for split-bf16)
-//   bit 2     global_match_bf16_kernel: register staging instead of LDS-DMA
-//   bit 3     static s_setprio 1 for waves 4-7 (8-wave kernels)
-//   bit 4     plain bf16 on global_match_bf16_kernel (the un-pipelined loop)
-//   bit 6     plain bf16 on global_match_bf16_pipe_kernel (8 waves, 64 x 64 wave tile)
-// MANET_TUNE_ABLATION (key 3) selects the timing-ablation instantiations of the two pipelined kernels.
+// plain bf16 -> global_match_bf16_wide_kernel (k-steps 2 / 7), global_match_bf16_pipe_kernel for C > 106 (k-step 9: its
+// 144 operand VGPRs do not fit the wide form); split-bf16 -> global_match_bf16x3_kernel.
 template <int KSB, bool X3>
 void launch_main_bf16(const char *qpack, const char *bpack, const int *meta, int n_ids, int nQT, int S, long N_pad,
                       unsigned *keys, hipStream_t st, int prof_channel = 0)
 {
-#ifdef MANET_ABLATION
-    const int v = manet_tune_get(MANET_TUNE_BF16_VARIANT, 0);
-#else
-    const int v = 0;  // (the default build carries the shipped kernels only: make EXTRA=-DMANET_ABLATION for the rest)
-#endif
-    const int flat = (v >> 4) & 1;
-    int prio = (v >> 3) & 1;
-    if constexpr (!X3) {
-        if (!flat) {  // plain-bf16 kernels: software-pipelined fragments, barrier in front of the step's last pass
-            // the 8-wave 64x64-wave-tile form: KSB = 9 (C > 106), whose 144 operand VGPRs do not fit the wide form; tuning
-            constexpr bool NARROW_ONLY = (KSB == 9);
-            const bool narrow = NARROW_ONLY || ((v >> 6) & 1);
-            const void *fn = nullptr;
-#ifdef MANET_ABLATION
-            const int abl = KSB == 7 ? manet_tune_get(MANET_TUNE_ABLATION, 0) : 0;  // timing experiments only
-            if (narrow) {
-#define MANET_PK(AB_) \
-    if (abl == AB_) fn = (const void *)global_match_bf16_pipe_kernel<KSB, (KSB == 7 ? AB_ : 0)>;
-                MANET_PK(0) MANET_PK(1) MANET_PK(2) MANET_PK(4) MANET_PK(8) MANET_PK(15)
-#undef MANET_PK
-                if (!fn) fn = (const void *)global_match_bf16_pipe_kernel<KSB, 0>;
-            } else if constexpr (!NARROW_ONLY) {
-#define MANET_WK(AB_) \
-    if (abl == AB_) fn = (const void *)global_match_bf16_wide_kernel<KSB, (KSB == 7 ? AB_ : 0)>;
-                MANET_WK(0) MANET_WK(1) MANET_WK(2) MANET_WK(4) MANET_WK(8) MANET_WK(15)
-#undef MANET_WK
-                if (!fn) fn = (const void *)global_match_bf16_wide_kernel<KSB, 0>;
-            }
-#else
-            if constexpr (NARROW_ONLY) fn = (const void *)global_match_bf16_pipe_kernel<KSB, 0>;
-            else fn = (const void *)global_match_bf16_wide_kernel<KSB, 0>;
-#endif
-            const unsigned threads = narrow ? 512 : 256;
-            const size_t lds = (size_t)2 * 2 * bank_tile_bytes_u(2 * KSB, false);
-            (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            int bm = block_map_arg(nQT, narrow ? 256 : 512, S);
-            unsigned *no_thr = nullptr;
-            const float *no_slack = nullptr;
-            unsigned long long *no_stats = nullptr;
-            uint2 *no_list = nullptr;
-            unsigned *no_bcnt = nullptr;
-            long no_cap = 0;
-            // (the narrow kernel takes the first ten arguments; the wide one also the FILTER form's five, unused here)
-            void *args[] = {(void *)&qpack, (void *)&bpack, (void *)&meta, (void *)&n_ids, (void *)&nQT, (void *)&S,
-                            (void *)&N_pad, (void *)&keys, (void *)&bm, (void *)&prio, (void *)&no_thr, (void *)&no_slack,
-                            (void *)&no_stats, (void *)&no_list, (void *)&no_cap, (void *)&no_bcnt};
-            manet_profile_record(st, true, prof_channel);
-            (void)hipLaunchKernel(fn, dim3((unsigned)(nQT * S)), dim3(threads), args, lds, st);
-            manet_profile_record(st, false, prof_channel);
-            return;
-        }
+    const dim3 grid((unsigned)(nQT * S));
+    if constexpr (X3) {
+        const size_t lds = 2 * bank_tile_bytes_u(4 * KSB, false);
+        (void)hipFuncSetAttribute((const void *)global_match_bf16x3_kernel<KSB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        manet_profile_record(st, true, prof_channel);
+        hipLaunchKernelGGL((global_match_bf16x3_kernel<KSB>), grid, dim3(512), lds, st, qpack, bpack, meta, n_ids, nQT, S, N_pad, keys,
+                           block_map_arg(nQT, 256, S));
+        manet_profile_record(st, false, prof_channel);
+    } else if constexpr (KSB == 9) {
+        const size_t lds = (size_t)2 * 2 * bank_tile_bytes_u(2 * KSB, false);
+        (void)hipFuncSetAttribute((const void *)global_match_bf16_pipe_kernel<KSB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        manet_profile_record(st, true, prof_channel);
+        hipLaunchKernelGGL((global_match_bf16_pipe_kernel<KSB>), grid, dim3(512), lds, st, qpack, bpack, meta, n_ids, nQT, S, N_pad, keys,
+                           block_map_arg(nQT, 256, S));
+        manet_profile_record(st, false, prof_channel);
+    } else {
+        const size_t lds = (size_t)2 * 2 * bank_tile_bytes_u(2 * KSB, false);
+        (void)hipFuncSetAttribute((const void *)global_match_bf16_wide_kernel<KSB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        manet_profile_record(st, true, prof_channel);
+        // (the FILTER form's six arguments are unused here)
+        hipLaunchKernelGGL((global_match_bf16_wide_kernel<KSB>), grid, dim3(256), lds, st, qpack, bpack, meta, n_ids, nQT, S, N_pad, keys,
+                           block_map_arg(nQT, 512, S), (unsigned *)nullptr, (const float *)nullptr, (unsigned long long *)nullptr,
+                           (uint2 *)nullptr, 0L, (unsigned *)nullptr);
+        manet_profile_record(st, false, prof_channel);
     }
-#ifdef MANET_ABLATION
-    const int tps = v & 3, reg = (v >> 2) & 1;
-#define MANET_BV(TPS_)                                                                                         \
-    if (reg) launch_main_bf16_v<KSB, X3, TPS_, false>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, prio, st); \
-    else launch_main_bf16_v<KSB, X3, TPS_, true>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, prio, st);
-    if (tps == 1) { MANET_BV(1) }
-    else if (tps == 2) { MANET_BV((X3 ? 2 : 4)) }
-    else { MANET_BV((X3 ? 1 : 2)) }
-#undef MANET_BV
-#else
-    // split-bf16: global_match_bf16_kernel<KSB, true, 1, true> (1 tile per step, asm LDS-DMA staging)
-    if constexpr (X3) launch_main_bf16_v<KSB, true, 1, true>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, prio, st);
-#endif
 }
 
 // MANET_COMPUTE_BF16_REFINE on a prepared bank (see the kernels' header comment).  `qimg` = the query's bf16 operand
@@ -3033,23 +2829,11 @@ int run_refine(const char *qimg, const void *qraw, int q_dtype, long q_sn, long 
     {
         const int S = pick_splits(ML.nQT, BL.T_max, 512);
         const size_t lds = (size_t)2 * 2 * bank_tile_bytes_u(2 * ML.G.steps, false) + (size_t)REFINE_LDS_LIST * 8 + 4 * 256 * 4;  // + the published keys
-        const void *fn = ML.G.steps == 2 ? (const void *)global_match_bf16_wide_kernel<2, 0, true>
-                                         : (const void *)global_match_bf16_wide_kernel<7, 0, true>;
-#ifdef MANET_ABLATION
-        if (ML.G.steps != 2) {  // timing experiments only (results are wrong): 16 no slow path, 32 no threshold exchange
-            const int fabl = manet_tune_get(MANET_TUNE_ABLATION, 0);
-            if (fabl == 16) fn = (const void *)global_match_bf16_wide_kernel<7, 16, true>;
-            if (fabl == 32) fn = (const void *)global_match_bf16_wide_kernel<7, 32, true>;
-            if (fabl == 48) fn = (const void *)global_match_bf16_wide_kernel<7, 48, true>;
-            if (fabl == 64) fn = (const void *)global_match_bf16_wide_kernel<7, 64, true>;    // no returning atomic in flush_sub
-            if (fabl == 128) fn = (const void *)global_match_bf16_wide_kernel<7, 128, true>;  // no listing behind the tests
-            if (fabl == 192) fn = (const void *)global_match_bf16_wide_kernel<7, 192, true>;
-            if (fabl == 256) fn = (const void *)global_match_bf16_wide_kernel<7, 256, true>;  // cycle counts of the listing path -> stats[4..9]
-        }
-#endif
+        const void *fn = ML.G.steps == 2 ? (const void *)global_match_bf16_wide_kernel<2, true>
+                                         : (const void *)global_match_bf16_wide_kernel<7, true>;
         (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         const char *bpack = bws + BL.off_pack;
-        int nQT = ML.nQT, Sv = S, bm = block_map_arg(ML.nQT, 512), prio = 0;
+        int nQT = ML.nQT, Sv = S, bm = block_map_arg(ML.nQT, 512);
         // (see split_of_block) the spread map.  (PB splits fastest on top of it, as the plain kernels have it: fabric fetch
         // of this pass 301 -> 176 MB at cfg3 shape, but concurrent splits of one object share thresholds later --
         // 4.3 -> 5.05 candidate rows per pair -- and the step got 1 % slower: not taken.)
@@ -3065,14 +2849,11 @@ int run_refine(const char *qimg, const void *qraw, int q_dtype, long q_sn, long 
         unsigned *thr_c = thr;
         const float *slack_c = slack;
         void *args[] = {(void *)&qimg, (void *)&bpack, (void *)&meta, (void *)&n_ids, (void *)&nQT, (void *)&Sv,
-                        (void *)&N_pad, (void *)&keys, (void *)&bm, (void *)&prio, (void *)&thr_c, (void *)&slack_c, (void *)&stats,
+                        (void *)&N_pad, (void *)&keys, (void *)&bm, (void *)&thr_c, (void *)&slack_c, (void *)&stats,
                         (void *)&list, (void *)&cap, (void *)&bcnt};
         manet_profile_record(st, true, 0);
         (void)hipLaunchKernel(fn, dim3(fgrid), dim3(256), args, lds, st);
         manet_profile_record(st, false, 0);
-#ifdef MANET_ABLATION
-        if (manet_tune_get(MANET_TUNE_ABLATION, 0) == 256) hipLaunchKernelGGL(refine_debug_kernel, dim3(1), dim3(1), 0, st, stats);
-#endif
     }
     }  // (!force_exact)
     // 4. exact re-rank of the candidates
@@ -3204,11 +2985,6 @@ static int frame_prepare_impl(const void *emb, int emb_dtype, int64_t s_f, int64
     if (fill_words < 0 || (fill_words > 0 && !fill_ptr)) return manet_set_error(MANET_E_INVALID, "bad fill request");
     const ManetFrameLayout F = manet_frame_layout(h, w, C, compute, max_distance);
     const Geom G = geom_of(C, compute);
-#ifdef MANET_ABLATION
-    const int XC = manet_tune_get(MANET_TUNE_FRAME_XC, 0) == 1 ? 64 : 32;  // (tuning: 64-column workgroups)
-#else
-    const int XC = 32;
-#endif
     FramePrep A;
     A.emb = emb;
     A.s_f = (long)s_f; A.s_y = (long)s_y; A.s_x = (long)s_x; A.s_c = (long)s_c;
@@ -3220,11 +2996,7 @@ static int frame_prepare_impl(const void *emb, int emb_dtype, int64_t s_f, int64
     A.N = (long)h * w; A.N_pad = F.N_pad;
     A.fill_ptr = (unsigned *)fill_ptr; A.fill_words = (long)fill_words; A.fill_value = fill_value;
     A.nxc = (w + XC - 1) / XC;
-#ifdef MANET_ABLATION
-    A.abl = manet_tune_get(MANET_TUNE_ABLATION, 0);
-#else
     A.abl = 0;
-#endif
     A.n_data = ((h + 1) / 2) * A.nxc;
     long aux_items = (long)(F.N_pad - A.N) * G.units + fill_words + 64;
     if (max_distance >= 0) aux_items += (long)C * (F.HPAD - F.hp) * (F.WS / 4) + (long)C * F.hp * (F.WS - F.wp) / 4;
@@ -3244,16 +3016,9 @@ static int frame_prepare_impl(const void *emb, int emb_dtype, int64_t s_f, int64
     if (emb_dtype != MANET_EMB_F32 && emb_dtype != MANET_EMB_BF16)
         return manet_set_error(MANET_E_INVALID, "embedding dtype %d (MANET_EMB_F32 / MANET_EMB_BF16)", emb_dtype);
     const void *fn = emb_dtype == MANET_EMB_F32
-                         ? (A.vec2 ? (const void *)frame_prepare_kernel<float, 32, true> : (const void *)frame_prepare_kernel<float, 32, false>)
-                         : (A.vec2 ? (const void *)frame_prepare_kernel<unsigned short, 32, true>
-                                   : (const void *)frame_prepare_kernel<unsigned short, 32, false>);
-#ifdef MANET_ABLATION
-    if (XC == 64)
-        fn = emb_dtype == MANET_EMB_F32
-                 ? (A.vec2 ? (const void *)frame_prepare_kernel<float, 64, true> : (const void *)frame_prepare_kernel<float, 64, false>)
-                 : (A.vec2 ? (const void *)frame_prepare_kernel<unsigned short, 64, true>
-                           : (const void *)frame_prepare_kernel<unsigned short, 64, false>);
-#endif
+                         ? (A.vec2 ? (const void *)frame_prepare_kernel<float, true> : (const void *)frame_prepare_kernel<float, false>)
+                         : (A.vec2 ? (const void *)frame_prepare_kernel<unsigned short, true>
+                                   : (const void *)frame_prepare_kernel<unsigned short, false>);
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     void *args[] = {(void *)&A};
     manet_profile_record(st, true, 2);
@@ -3426,14 +3191,8 @@ int manet_global_match_prepared_ex(const void *query, int emb_dtype, int64_t q_s
                           mem_inout, epilogue_flags, st);
     }
     // resident workgroup slots: f32 and plain bf16 (wide kernel) = 2 x 256-thread workgroups per CU,
-    // split-bf16 (and the tuning-only narrow/flat bf16 forms) = 1 x 512-thread workgroup per CU
-#ifdef MANET_ABLATION
-    const int bv = manet_tune_get(MANET_TUNE_BF16_VARIANT, 0);
-#else
-    const int bv = 0;
-#endif
-    const bool two_per_cu = compute == MANET_COMPUTE_F32 ||
-                            (compute == MANET_COMPUTE_BF16 && !(bv & (16 | 64)) && ML.G.steps != 9);
+    // split-bf16 and the narrow plain-bf16 kernel (C > 106) = 1 x 512-thread workgroup per CU
+    const bool two_per_cu = compute == MANET_COMPUTE_F32 || (compute == MANET_COMPUTE_BF16 && ML.G.steps != 9);
     int S = pick_splits(ML.nQT, BL.T_max, two_per_cu ? 512 : 256);
     tl_bank_bytes_hint = (double)BL.T_max * (double)BL.tile_bytes;  // (block_map_arg)
     {
@@ -3464,29 +3223,19 @@ int manet_global_match_prepared_ex(const void *query, int emb_dtype, int64_t q_s
         }
 #undef MANET_GB_CASE
     } else {
-#ifdef MANET_ABLATION
-        const bool pipe = !manet_tune_get(MANET_TUNE_F32_UNPIPED, 0);  // tuning: 1 = the un-pipelined k = 1 kernel
-#define MANET_GM_UNPIPED(KS_) launch_main_f32<KS_, 1>(qpack, bpack, meta, n_ids, ML.nQT, S, ML.N_pad, keys, topk, st)
-#else
-        const bool pipe = true;
-#define MANET_GM_UNPIPED(KS_) (void)0
-#endif
 #define MANET_GM_CASE(KS_)                                                                                    \
     case KS_:                                                                                                 \
-        if (k_nn == 1 && pipe) launch_main_f32_pipe<KS_>(qpack, bpack, meta, n_ids, ML.nQT, S, ML.N_pad, keys, st); \
-        else if (k_nn == 1) MANET_GM_UNPIPED(KS_);                                                            \
+        if (k_nn == 1) launch_main_f32_pipe<KS_>(qpack, bpack, meta, n_ids, ML.nQT, S, ML.N_pad, keys, st);   \
         else launch_main_f32<KS_, MANET_MAX_KNN>(qpack, bpack, meta, n_ids, ML.nQT, S, ML.N_pad, keys, topk, st); \
         break;
     switch (pick_ks(C)) {
         MANET_GM_CASE(16) MANET_GM_CASE(50) MANET_GM_CASE(52)
     default:
-        if (k_nn == 1 && pipe) launch_main_f32_pipe<64>(qpack, bpack, meta, n_ids, ML.nQT, S, ML.N_pad, keys, st);
-        else if (k_nn == 1) MANET_GM_UNPIPED(64);
+        if (k_nn == 1) launch_main_f32_pipe<64>(qpack, bpack, meta, n_ids, ML.nQT, S, ML.N_pad, keys, st);
         else launch_main_f32<64, MANET_MAX_KNN>(qpack, bpack, meta, n_ids, ML.nQT, S, ML.N_pad, keys, topk, st);
         break;
     }
 #undef MANET_GM_CASE
-#undef MANET_GM_UNPIPED
     }
     long total = (long)(armed ? ML.N_pad : N) * n_ids;
     if (k_nn == 1)

@@ -101,24 +101,14 @@ __host__ __device__ constexpr size_t lf_lds_phase2_bytes(int d, int rows, int m2
            (size_t)lf_npix(d) * (m2_rows + 1) * 4 + (size_t)(2 * (lf_sy(d) - 1) + 4 + 2 * (LF_SX - 1) + 4) * 16 +
            (size_t)lf_lab_rows_of(d, rows) * 16;
 }
-// The per-pixel phase ON A STORED VOLUME (the kernel's LF_VOL_IN mode, r6) can deal the window rows of an image to lf_nsub(d) workgroups of
-// lf_ndv(d) rows each (two or more then fit a CU).  Measured at 480p, d = 12 (docs/history/r06_experiments.md): 5 rows per workgroup
-// (one wave of 240 workgroups) 21.1 us; 2 rows (720 workgroups, two per CU) 23.8; 1 row (1 200, four per CU) 26-30 -- every
-// workgroup pays the label fetch, the tables, the minima's initialisation and the closing atomics again, and those, not the volume
-// stream, are what a workgroup waits for.  Shipped: no split (lf_ndv = lf_nd).  The fp16 image keeps the split and the thread count
-// of the fp32 one (half the pieces per workgroup; the counted waits are derived from the piece count, not written down).
-#ifndef MANET_LF_NDV12
-#define MANET_LF_NDV12 5  // (A/B builds: window rows per workgroup of the stored-volume kernel at d = 12)
-#endif
-#ifndef MANET_LF_NTV
-#define MANET_LF_NTV 0    // (A/B builds: threads per workgroup of the stored-volume kernel at d >= 10; 0 = the fused kernel's)
-#endif
-__host__ __device__ constexpr int lf_ndv(int d) { return d == 12 ? MANET_LF_NDV12 : lf_nd(d); }
-__host__ __device__ constexpr int lf_ntv(int d) { return (MANET_LF_NTV > 0 && d >= 10) ? MANET_LF_NTV : lf_nt(d); }
-__host__ __device__ constexpr int lf_nsub(int d) { return (lf_nd(d) + lf_ndv(d) - 1) / lf_ndv(d); }
+// The per-pixel phase ON A STORED VOLUME (the kernel's LF_VOL_IN mode, r6) runs one workgroup per (tile, window-row group), as the fused
+// kernel does.  Dealing a group's rows to several workgroups was measured slower at 480p, d = 12 (docs/history/r06_experiments.md): 5 rows
+// per workgroup 21.1 us, 2 rows 23.8, 1 row 26-30 -- every workgroup pays the label fetch, the tables, the minima's initialisation and
+// the closing atomics again.  The fp16 image keeps the thread count of the fp32 one (half the pieces per workgroup; the counted waits
+// are derived from the piece count).
 __host__ __device__ constexpr size_t lf_lds_vol_bytes(int d, int n_ids, size_t es = 4)
 {
-    return lf_lds_phase2_bytes(d, lf_ndv(d), n_ids <= LF_NIP ? n_ids : LF_NIP, es);
+    return lf_lds_phase2_bytes(d, lf_nd(d), n_ids <= LF_NIP ? n_ids : LF_NIP, es);
 }
 __host__ __device__ constexpr size_t lf_lds_bytes(int d)
 {

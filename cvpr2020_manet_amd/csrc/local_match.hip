@@ -383,15 +383,6 @@ __global__ void lf_pool_pad_kernel(const SRC *__restrict__ a, long a_sy, long a_
     bp[i] = vb;
 }
 
-// Phase timeline of the fused kernel (development aid, off by default): build with
-// `make -C cvpr2020_manet_amd/csrc EXTRA=-DMANET_LF_TIMELINE`, run tools/local_timeline.py on the GPU box.
-#ifdef MANET_LF_TIMELINE
-__device__ unsigned long long lf_dbg[8192 * 8];
-extern "C" int manet_dbg_read(unsigned long long *host, size_t n) { return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(lf_dbg), n * 8); }
-#define LF_T(k) if (threadIdx.x == 0) lf_dbg[blockIdx.x * 8 + (k)] = wall_clock64();
-#else
-#define LF_T(k)
-#endif
 // MODE (r6): the window distances depend on the two EMBEDDINGS only (IntVOS.py:266-296), the masked minimum (:398-432) on the
 // previous frame's labels -- and a clip's embeddings never change between the interaction rounds of a session (test.py:137-154
 // extracts them once per sequence).  LF_VOL_OUT: phase 1 alone, for a BATCH of frame pairs in one launch (blockIdx.y = pair): each
@@ -464,7 +455,7 @@ using LfExtra = typename std::conditional<MODE == LF_VOL_OUT, LfBatch, typename 
 template <int D, int MODE, typename VT>
 __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, const float *__restrict__ prevp_arg, int WS, long PS,
                                         const int *__restrict__ labels, int h, int w, int C, int n_ids, float *__restrict__ out,
-                                        const int *__restrict__ tab, int abl_arg, int ntx, int nty, int rw, int rh,
+                                        const int *__restrict__ tab, int /* always 0 */, int ntx, int nty, int rw, int rh,
                                         VT *__restrict__ vol_arg, const LfExtra<MODE> batch)
 {
     static_assert(sizeof(VT) == 4 || MODE != LF_FUSED, "the fp16 image exists in memory only");
@@ -476,14 +467,8 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
         prevp = batch.prev[blockIdx.y];
         vol = (VT *)batch.vol[blockIdx.y];
     }
-    // (the ablation switch is a compile-time 0 outside -DMANET_ABLATION builds: no run-time tests in the loops)
-#ifdef MANET_ABLATION
-    const int abl = abl_arg;
-#else
-    constexpr int abl = 0;
-#endif
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    constexpr int P = 2 * D + 1, NT = MODE == LF_VOL_IN ? lf_ntv(D) : lf_nt(D), ND = lf_nd(D), NDG = lf_ndg(D), SY = lf_sy(D), TY = SY - 1;
+    constexpr int P = 2 * D + 1, NT = lf_nt(D), ND = lf_nd(D), NDG = lf_ndg(D), SY = lf_sy(D), TY = SY - 1;
     constexpr int TX = LF_SX - 1, CW = lf_cw(D), YR = lf_yr(D), CC = lf_cc(D), COLS = lf_cols(D), NG = LF_SX / COLS;
     constexpr int DXS = lf_dxs(D), PA = lf_pa(D), LF_PH = lf_ph(D);
     constexpr int yplane = YR * CW, xplane = SY * LF_SX;
@@ -494,7 +479,6 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
     constexpr int buf_floats = lf_stage_floats(D);             // = NPIECE * 256
     float *smem = (float *)smem_raw;
     const int tid = threadIdx.x;
-    LF_T(0)
     const int hp = h / 2, wp = w / 2;
     // XCD-aware block -> (tile column, tile row, window-row group): block L runs on XCD L % 8 (observed, used for speed
     // only), whose L2 serves the staging DMA.  Each XCD gets a compact rw x rh block of tiles (4 x 2 such regions cover the
@@ -502,18 +486,14 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
     // of a full-height strip per tile column -- r3 PMC at 480p, d=12: the kernel's fabric fetch 33 -> 22 MB.
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
     const int tix = (xcd & 3) * rw + idx % rw, tmp_ = idx / rw;
-    // LF_VOL_IN: an image's window rows are dealt to NSUB workgroups of NDR rows (lf_ndv): two of them fit a CU
-    constexpr int NDR = MODE == LF_VOL_IN ? lf_ndv(D) : ND, NSUB = MODE == LF_VOL_IN ? lf_nsub(D) : 1;
-    const int tiy = (xcd >> 2) * rh + tmp_ % rh, tizs = tmp_ / rh;
-    const int tiz = tizs / NSUB, sub = tizs - tiz * NSUB;
+    const int tiy = (xcd >> 2) * rh + tmp_ % rh, tiz = tmp_ / rh;
     if (tix >= ntx || tiy >= nty) return;  // (the regions' padding)
     const int a = tiy * TY, b0 = tix * TX;  // pooled origin of S
-    const int dy0 = tiz * ND + sub * NDR;   // first window row of this workgroup
-    // window rows this workgroup really owns (the last group of an image / the last image of a tile may hold fewer)
-    const int nd_here = min(min(P - dy0, ND - sub * NDR), NDR);
+    const int dy0 = tiz * ND;  // first window row of this workgroup
+    // window rows this workgroup really owns (the last image of a tile may hold fewer)
+    const int nd_here = min(P - dy0, ND);
     if (nd_here <= 0) return;
-    VT *vimg = MODE == LF_FUSED ? nullptr
-                                : vol + (long)((tiz * nty + tiy) * ntx + tix) * lf_img_elems<VT>(D) + (long)sub * NDR * (SY * LF_SX * lf_vs(D));
+    VT *vimg = MODE == LF_FUSED ? nullptr : vol + (long)((tiz * nty + tiy) * ntx + tix) * lf_img_elems<VT>(D);
 
     // ---- phase 1: distances on S for window rows dy0 .. dy0+ND-1 ---------------------------------
     // Staging by LDS-DMA (lds_dma16: 64 lanes x 16 bytes land in 1 KiB of LDS, no VGPR hop, no ds_write): a stage is
@@ -592,7 +572,7 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
         float xv[COLS];
     };
     auto compute = [&](int buf_, int nch) __attribute__((always_inline)) {
-        if (active && !(abl & 1)) {
+        if (active) {
         const float *ys = smem + (long)buf_ * buf_floats + (ry + dyi) * CW + COLS * g + dx_lo;
         const float *xs = smem + (long)buf_ * buf_floats + CC * yplane + ry * LF_SX + COLS * g;
         auto fetch = [&](Chan &W, int c) __attribute__((always_inline)) {
@@ -670,17 +650,14 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
     // window-row group), all pieces; then counted waits: the labels (oldest) -> label bytes, change masks, tables, minima; the first
     // VR1 window rows -> their items; the rest -> the other items.  The launch is one wave of workgroups: without this every
     // workgroup waited 7 us for the whole 25.8 MB and then all of them computed (timeline in docs/history/r06_experiments.md).
-    constexpr int VR1 = (2 * NDR) / 5 > 0 ? (2 * NDR) / 5 : 1;  // window rows whose items start first
-    constexpr int IMG_PIECES = (int)(lf_vpad_bytes(D, NDR, sizeof(VT)) / 1024);  // (whole 1 KiB pieces: the tail lands in the V region's padding)
-    // the fetch of an image's LAST row group ends at most 1 KiB behind the image: the slack manet_local_volume_bytes[_f16] adds behind
-    // the last image (true for lf_nsub = 1 and for any lf_ndv that divides lf_nd; a split that leaves a partial group would overrun)
-    static_assert(MODE != LF_VOL_IN || (size_t)(NSUB - 1) * NDR * SY * LF_SX * lf_vs(D) * sizeof(VT) + (size_t)IMG_PIECES * 1024 <=
-                                           (size_t)lf_img_elems<VT>(D) * sizeof(VT) + 1024,
+    constexpr int VR1 = (2 * ND) / 5 > 0 ? (2 * ND) / 5 : 1;  // window rows whose items start first
+    constexpr int IMG_PIECES = (int)(lf_vpad_bytes(D, ND, sizeof(VT)) / 1024);  // (whole 1 KiB pieces: the tail lands in the V region's padding)
+    // the fetch of an image ends at most 1 KiB behind it: the slack manet_local_volume_bytes[_f16] adds behind the last image
+    static_assert(MODE != LF_VOL_IN || (size_t)IMG_PIECES * 1024 <= (size_t)lf_img_elems<VT>(D) * sizeof(VT) + 1024,
                   "the stored-volume tail would fetch past the volume's 1 KiB of slack");
-    constexpr int IMG_P1 = NDR > VR1 ? (VR1 * SY * LF_SX * lf_vs(D) * (int)sizeof(VT) + 1023) / 1024 : IMG_PIECES;
+    constexpr int IMG_P1 = ND > VR1 ? (VR1 * SY * LF_SX * lf_vs(D) * (int)sizeof(VT) + 1023) / 1024 : IMG_PIECES;
     // this wave's pieces among the first x pieces of the image (dealt round-robin)
     auto my_pieces = [&](int x) __attribute__((always_inline)) { return x > wave ? (x - wave + NWV - 1) / NWV : 0; };
-    LF_T(1)
     // full-resolution pixels of this tile: rows with i0(y) in [a, a+TY), columns with j0(x) in [b0, b0+TX) -- the
     // pooling pass left the ranges in `tab`
     int ya = 0, yb = 0, xa = 0, xb = 0;
@@ -701,8 +678,8 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
     // the previous frame's labels around the tile: rows ya + 2(dy0 - D) .., columns xa - 2D ..; outside the image = 0
     // (zero padding, IntVOS.py:400).  Loaded NOW (behind the first two stages' loads, under the first stage's arithmetic), used after phase 1: they come
     // from HBM (nobody has touched them this frame) and would otherwise cost a full miss latency between the phases
-    constexpr int KL = (lf_lab_rows_of(D, NDR) * lf_lab_cols(D) + NT - 1) / NT;
-    const int lrows = ny + 2 * (NDR - 1), lcols = nx + 4 * D;
+    constexpr int KL = (lf_lab_rows_of(D, ND) * lf_lab_cols(D) + NT - 1) / NT;
+    const int lrows = ny + 2 * (ND - 1), lcols = nx + 4 * D;
     const int ly0 = ya + 2 * (dy0 - D), lx0 = xa - 2 * D;
     int labr[KL];
 #pragma unroll
@@ -720,7 +697,7 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
             asm volatile("global_load_dword %0, %1, %2" : "=v"(v) : "v"(boff), "s"(labels) : "memory");
             labr[k] = v;  // (masked below, after the wait: the asm load's result must not be touched before it)
         } else {
-            labr[k] = (yy == yc && xx == xc && !(abl & 8)) ? v : 0;
+            labr[k] = (yy == yc && xx == xc) ? v : 0;
         }
     }
     if constexpr (MODE == LF_VOL_IN) {
@@ -735,7 +712,7 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
             const int r = e / lcols, c = e - r * lcols;
             const int yy = ly0 + r, xx = lx0 + c;
             const bool inside = yy >= 0 && yy < h && xx >= 0 && xx < w;
-            labr[k] = (inside && !(abl & 8)) ? labr[k] : 0;
+            labr[k] = inside ? labr[k] : 0;
         }
     }
 
@@ -743,7 +720,7 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
     // barrier) is issued first and runs under the arithmetic of stage s; the wave waits for its own pieces (vmcnt --
     // the DMA is hidden from the compiler's counters, this is the only wait on it) and the barrier publishes them.
     if constexpr (MODE != LF_VOL_IN) {
-        for (int c0 = 0, st_i = 0; c0 < ((abl & 16) ? 0 : C); c0 += CC, ++st_i) {
+        for (int c0 = 0, st_i = 0; c0 < C; c0 += CC, ++st_i) {
             if (c0 + CC < C) stage_dma(c0 + CC, (st_i & 1) ^ 1);
             compute(st_i & 1, (C - c0) < CC ? (C - c0) : CC);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -751,10 +728,9 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
         }
     }
 
-    LF_T(2)
     constexpr int VS = lf_vs(D), NPS = lf_npix(D);
-    VT *V = (VT *)smem;                                              // [NDR][SY * 16][VS] (+ the tail of the last LDS-DMA piece)
-    unsigned char *L = (unsigned char *)smem + lf_vpad_bytes(D, NDR, sizeof(VT));  // [lab_rows][lab_cols]; a byte >= the pass's ids = "no id"
+    VT *V = (VT *)smem;                                              // [ND][SY * 16][VS] (+ the tail of the last LDS-DMA piece)
+    unsigned char *L = (unsigned char *)smem + lf_vpad_bytes(D, ND, sizeof(VT));  // [lab_rows][lab_cols]; a byte >= the pass's ids = "no id"
     if (MODE != LF_VOL_IN && active) {
         VT *vp0 = V + ((dyi * SY + ry) * LF_SX + COLS * g) * VS + dx_lo;
 #pragma unroll
@@ -764,7 +740,7 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
                 if (LF_PH % 4 == 0 && d4 + 3 < PA && d4 + 3 < ndx) {
                     f32x4 t;
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) t[i] = (abl & 4) ? LF_ACC(j, d4 + i) : manet_normalize_dist_local(LF_ACC(j, d4 + i));
+                    for (int i = 0; i < 4; ++i) t[i] = manet_normalize_dist_local(LF_ACC(j, d4 + i));
                     if constexpr (F16) *(lf_h4 *)(vp0 + j * VS + d4) = __builtin_convertvector(t, lf_h4);  // v_cvt_f16_f32: to nearest even
                     else *(f32x4 *)(vp0 + j * VS + d4) = t;
                 } else {
@@ -775,7 +751,6 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
             }
         }
     }
-    LF_T(3)
     if constexpr (MODE == LF_VOL_OUT) {
         // the image as phase 2 reads it, to memory in one linear pass (entries no thread wrote -- the cells' padding past the
         // window width, window rows past 2d+1 in the last group -- travel along and are never used)
@@ -791,10 +766,9 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
         const int lmax = n_ids <= LF_NIP ? n_ids : 255;
         if (e < lrows * lcols) L[e] = (labr[k] >= 0 && labr[k] < (n_ids <= LF_NIP ? n_ids : MANET_MAX_IDS)) ? (unsigned char)labr[k] : (unsigned char)lmax;
     }
-    LF_T(7)
     // per-(id, pixel) minima [LF_NIP + 1][NPS] (row LF_NIP collects the candidates whose label is not an id of this
     // pass), then the separable bilinear tables: tap offsets into V and the two weights, per pixel row / column
-    unsigned *M2 = (unsigned *)(L + (((size_t)lf_lab_rows_of(D, NDR) * lf_lab_cols(D) + 15) & ~(size_t)15));
+    unsigned *M2 = (unsigned *)(L + (((size_t)lf_lab_rows_of(D, ND) * lf_lab_cols(D) + 15) & ~(size_t)15));
     const int m2_rows = n_ids <= LF_NIP ? n_ids : LF_NIP;  // + the "no id" row (the launcher sized the LDS for it)
     struct Tap {
         int o0, o1;
@@ -837,11 +811,10 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
         // (LF_VOL_IN: this wave's pieces of the first VR1 window rows have landed; the barrier publishes everyone's)
         if constexpr (MODE == LF_VOL_IN) lf_wait_vmcnt(my_pieces(IMG_PIECES) - my_pieces(IMG_P1));
         __syncthreads();
-        LF_T(4)
         // n_ids <= LF_NIP (one pass): the label byte, clamped to LF_NIP, IS the row of M2
         auto items = [&](auto single_pass, int item_lo, int item_hi) __attribute__((always_inline)) {
             constexpr bool SINGLE = decltype(single_pass)::value;
-            for (int item = item_lo + tid; item < ((abl & 2) ? 0 : item_hi); item += NT) {
+            for (int item = item_lo + tid; item < item_hi; item += NT) {
                 const int by = (int)(((float)item + 0.5f) * inv_npix), pix = item - by * npix;
                 const int py = (int)(((float)pix + 0.5f) * inv_nx), pxx = pix - py * nx;
                 const Tap r = RT[py], c = CT[pxx];
@@ -855,7 +828,7 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
                     // row's minimum in registers, one atomic.  Same candidates, same minimum: the same bits.
                     const unsigned long long cm = CM[2 * (py + 2 * by) + (pxx & 1)];
                     const bool mixed = ((cm >> (pxx >> 1)) & ((1ull << (P - 1)) - 1ull)) != 0ull;
-                    if (__builtin_amdgcn_ballot_w64(mixed) == 0ull && !(abl & 32)) {
+                    if (__builtin_amdgcn_ballot_w64(mixed) == 0ull) {
                         float m_ = INFINITY;
 #pragma unroll
                         for (int q = 0; q < (P + 3) / 4; ++q) {
@@ -908,26 +881,24 @@ __device__ __forceinline__ void lf_body(const float *__restrict__ curp_arg, cons
             }
         };
         // (LF_VOL_IN: the first batch's rows, then -- once the second batch has landed -- the others)
-        const int item_mid = (MODE == LF_VOL_IN && NDR > VR1) ? npix * (nd_here < VR1 ? nd_here : VR1) : npix * nd_here;
+        const int item_mid = (MODE == LF_VOL_IN && ND > VR1) ? npix * (nd_here < VR1 ? nd_here : VR1) : npix * nd_here;
         if (n_ids <= LF_NIP) items(std::true_type{}, 0, item_mid);
         else items(std::false_type{}, 0, item_mid);
-        if constexpr (MODE == LF_VOL_IN && NDR > VR1) {
+        if constexpr (MODE == LF_VOL_IN && ND > VR1) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (n_ids <= LF_NIP) items(std::true_type{}, item_mid, npix * nd_here);
             else items(std::false_type{}, item_mid, npix * nd_here);
         }
         __syncthreads();
-        LF_T(5)
         for (int e = tid; e < npix * nk; e += NT) {
             const int pix = e / nk, k = e - pix * nk;
             const int py = pix / nx, pxx = pix - py * nx;
             float *o = out + ((long)(ya + py) * w + (xa + pxx)) * n_ids + o0 + k;
-            if (NDG * NSUB == 1) *o = __uint_as_float(M2[k * NPS + pix]);
+            if (NDG == 1) *o = __uint_as_float(M2[k * NPS + pix]);
             else atomicMin((unsigned *)o, M2[k * NPS + pix]);  // several workgroups per tile: `out` was pre-set to 1.0
         }
         __syncthreads();
-        LF_T(6)
     }
 }
 
@@ -953,7 +924,6 @@ __global__ __launch_bounds__(lf_nt(D)) void local_fused_f16_kernel(const float *
                                                                    const LfExtra<MODE> batch)
 {
     static_assert(MODE == LF_VOL_OUT || MODE == LF_VOL_IN, "fp16 images are stored volumes");
-    static_assert(lf_ntv(D) <= lf_nt(D), "the launch bounds must cover the stored-volume tail's thread count");
     lf_body<D, MODE, _Float16>(curp_arg, prevp_arg, WS, PS, labels, h, w, C, n_ids, out, tab, abl_arg, ntx, nty, rw, rh, vol_arg, batch);
 }
 
@@ -971,13 +941,13 @@ static void launch_fused_d(hipStream_t st, const float *ap, const float *bp, con
     // i0 runs over 0..hp-1 (the last value only for the last row); tiles cover all of them
     const int ntx = (G.wp + TX - 1) / TX, nty = (G.hp + TY - 1) / TY;
     const int rw = (ntx + 3) / 4, rh = (nty + 1) / 2;  // tiles per XCD region (4 x 2 regions)
-    dim3 grid((unsigned)(8 * rw * rh * lf_ndg(D) * (MODE == LF_VOL_IN ? lf_nsub(D) : 1)), (unsigned)(MODE == LF_VOL_OUT ? n_pairs : 1));
+    dim3 grid((unsigned)(8 * rw * rh * lf_ndg(D)), (unsigned)(MODE == LF_VOL_OUT ? n_pairs : 1));
     const size_t lds = MODE == LF_VOL_IN ? lf_lds_vol_bytes(D, n_ids, sizeof(VT)) : lf_lds_bytes(D);
     (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)(MODE == LF_VOL_IN ? lf_lds_vol_bytes(D, LF_NIP, sizeof(VT)) : lds));
     if constexpr (MODE == LF_VOL_OUT)
         hipLaunchKernelGGL(kern, grid, dim3(lf_nt(D)), lds, st, ap, bp, G.WS, G.plane, labels, h, w, C, n_ids,
-                           out, tab, manet_tune_get(MANET_TUNE_ABLATION, 0), ntx, nty, rw, rh, vol, *batch);
+                           out, tab, 0, ntx, nty, rw, rh, vol, *batch);
     else if constexpr (MODE == LF_VOL_IN) {
         LfTab T;
         T.n = 0;
@@ -986,11 +956,11 @@ static void launch_fused_d(hipStream_t st, const float *ap, const float *bp, con
             for (int i = 0; i <= nty; ++i) T.v[i] = bilin_first(i * TY, G.hp, h);
             for (int i = 0; i <= ntx; ++i) T.v[nty + 1 + i] = bilin_first(i * TX, G.wp, w);
         }
-        hipLaunchKernelGGL(kern, grid, dim3(lf_ntv(D)), lds, st, ap, bp, G.WS, G.plane, labels, h, w, C, n_ids,
-                           out, tab, manet_tune_get(MANET_TUNE_ABLATION, 0), ntx, nty, rw, rh, vol, T);
+        hipLaunchKernelGGL(kern, grid, dim3(lf_nt(D)), lds, st, ap, bp, G.WS, G.plane, labels, h, w, C, n_ids,
+                           out, tab, 0, ntx, nty, rw, rh, vol, T);
     } else
         hipLaunchKernelGGL(kern, grid, dim3(lf_nt(D)), lds, st, ap, bp, G.WS,
-                           G.plane, labels, h, w, C, n_ids, out, tab, manet_tune_get(MANET_TUNE_ABLATION, 0), ntx, nty, rw, rh, vol, 0);
+                           G.plane, labels, h, w, C, n_ids, out, tab, 0, ntx, nty, rw, rh, vol, 0);
 }
 // workgroups (= volume images) of one frame pair
 static long lf_images(int h, int w, int d)
@@ -1484,7 +1454,7 @@ static int local_match_volume_t(const char *what, const VT *volume, const void *
     G.hp = F.hp; G.wp = F.wp; G.HPAD = F.HPAD; G.WS = F.WS; G.plane = F.PS;
     const int *tab = (const int *)((const char *)cur_frame_ws + F.off_tab);
     manet_profile_record(st, true, 1);
-    if (lf_ndg(max_distance) * lf_nsub(max_distance) > 1 && !out_is_preset) {  // partial minima of several workgroups per tile meet by atomicMin
+    if (lf_ndg(max_distance) > 1 && !out_is_preset) {  // partial minima of several workgroups per tile meet by atomicMin
         const long n_out = (long)h * w * n_ids;
         unsigned blocks = (unsigned)((n_out + 255) / 256);
         if (blocks > 1024) blocks = 1024;

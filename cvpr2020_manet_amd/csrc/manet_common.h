@@ -33,16 +33,13 @@ static inline int manet_check_launch(const char *what)
 // main kernel (channel 0) and the local-window stage (channel 1) are bracketed with two HIP events each.
 void manet_profile_record(hipStream_t st, bool start, int channel = 0);
 
-// tuning knobs (manet_tune_set; defaults are the shipped configuration)
-enum { MANET_TUNE_BLOCK_MAP = 0, MANET_TUNE_SPLITS = 1, MANET_TUNE_BF16_VARIANT = 2, MANET_TUNE_ABLATION = 3,
-       MANET_TUNE_LOCAL_UNFUSED = 4, MANET_TUNE_F32_UNPIPED = 5, MANET_TUNE_FRAME_XC = 6, MANET_TUNE_REFINE_SUB = 7,
+// tuning knobs (manet_tune_set; defaults are the shipped configuration).  The numbers are ABI (bench.py --tune and the tests pass
+// integers); 2, 3, 5, 6, 7, 9, 11 and 12 belonged to experiments that are closed and stay retired: manet_tune_set refuses them.
+enum { MANET_TUNE_BLOCK_MAP = 0, MANET_TUNE_SPLITS = 1, MANET_TUNE_LOCAL_UNFUSED = 4,
        MANET_TUNE_CONV1X1 = 8 /* 1: the LDS-weights 1x1 kernel even where the resident-weights one applies; 2-4: forms of the latter (seg_head.hip) */,
-       MANET_TUNE_RESCUE_SPLITS = 9 /* bank splits per listed tile of bf16r's rescue launch (experiments) */,
        MANET_TUNE_ONE_ROUND = 10 /* 1: the fp32 kernel keeps the host's split count whatever the bank's real size (A/B timing) */,
-       MANET_TUNE_RW_GROUPS = 11 /* resident-weights 1x1: pixel-range groups (default 256 = one per CU, two workgroups each) */,
-       MANET_TUNE_RW_LDS_PAD = 12 /* ... and KiB of unused dynamic LDS added to its launch (caps its workgroups per CU; experiments) */,
        MANET_TUNE_DW_NARROW = 13 /* 0: the depthwise kernel tiles a narrow last column with standard 60 x 64 tiles (r2-r5; A/B timing and tests) */,
-       MANET_TUNE_COUNT = 15 };
+       MANET_TUNE_COUNT = 14 };
 int manet_tune_get(int key, int dflt);
 
 // csrc/match_train.hip: masked minimum + winning window offset of the training forward on a normalised pooled volume

@@ -41,7 +41,13 @@ void manet_profile_record(hipStream_t st, bool start, int channel)
 
 static int g_tune[MANET_TUNE_COUNT] = {0};
 static bool g_tune_set[MANET_TUNE_COUNT] = {false};
-// experiments without touching a caller's code: MANET_TUNING=1 MANET_TUNE_INIT="11=128,12=17" sets knobs at the first read
+// the keys the data path reads; 2, 3, 5, 6, 7, 9, 11 and 12 selected experiment kernels and launch forms that are gone
+static bool tune_key_live(long key)
+{
+    return key == MANET_TUNE_BLOCK_MAP || key == MANET_TUNE_SPLITS || key == MANET_TUNE_LOCAL_UNFUSED || key == MANET_TUNE_CONV1X1 ||
+           key == MANET_TUNE_ONE_ROUND || key == MANET_TUNE_DW_NARROW;
+}
+// experiments without touching a caller's code: MANET_TUNING=1 MANET_TUNE_INIT="0=1,8=3" sets knobs at the first read
 static std::once_flag g_tune_env_once;
 static void tune_env_init()
 {
@@ -54,7 +60,7 @@ static void tune_env_init()
         p = end + 1;
         const long val = strtol(p, &end, 10);
         if (end == p) break;
-        if (key >= 0 && key < MANET_TUNE_COUNT) {
+        if (tune_key_live(key)) {  // (retired and out-of-range keys: ignored)
             g_tune[key] = (int)val;
             g_tune_set[key] = true;
         }
@@ -78,13 +84,7 @@ int manet_tune_set(int key, int value)
     if (!opt || opt[0] != '1')
         return manet_set_error(MANET_E_INVALID, "manet_tune_set is for experiments: set MANET_TUNING=1 in the environment");
     if (key < 0 || key >= MANET_TUNE_COUNT) return manet_set_error(MANET_E_INVALID, "tune key %d", key);
-#ifndef MANET_ABLATION
-    // the default build carries only the kernels the data path can reach; the variant / ablation instantiations these keys
-    // select are compiled in by `make EXTRA=-DMANET_ABLATION`
-    if (key == MANET_TUNE_BF16_VARIANT || key == MANET_TUNE_ABLATION || key == MANET_TUNE_F32_UNPIPED || key == MANET_TUNE_FRAME_XC)
-        return manet_set_error(MANET_E_INVALID, "tune key %d selects kernel variants this library was built without: rebuild "
-                                                "with `make -C cvpr2020_manet_amd/csrc clean all EXTRA=-DMANET_ABLATION`", key);
-#endif
+    if (!tune_key_live(key)) return manet_set_error(MANET_E_INVALID, "tune key %d was removed with the experiment it served", key);
     g_tune[key] = value;
     g_tune_set[key] = value != INT32_MIN;  // INT32_MIN: back to "not set" (the shipped default, e.g. the automatic block map)
     return MANET_OK;

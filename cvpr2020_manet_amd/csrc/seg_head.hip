@@ -51,7 +51,7 @@ constexpr int DW_TY = DwStd::TY, DW_TX = DwStd::TX, DW_IMG = DwStd::IMG;
 // (the 4-byte-load form of odd widths needs ~148 registers: three workgroups per CU -- at four it spilled 20 of them, r4)
 // RELU_IN / RELU (r5): compile-time -- as run-time flags each staged element paid a select on top of its max (76 v_cndmask +
 // 76 v_max per item against 392 packed FMAs), each output one more.  (Worth ~1 % on a warm GPU: the kernel hides it.)
-template <typename SH, bool FAST, bool RELU_IN, bool RELU, int ABL>
+template <typename SH, bool FAST, bool RELU_IN, bool RELU>
 __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *__restrict__ in, int C, int h, int w,
                                         const float *__restrict__ weight, const float *__restrict__ bias,
                                         const float *__restrict__ scale, const float *__restrict__ shift, float *__restrict__ out,
@@ -91,9 +91,7 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
             const int xx = x0 - 4 + 2 * (i - (i / NQ) * NQ);
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
-                if (ABL & 2) {
-                    ld[k][e] = f32x2{(float)off[k][e], (float)xx};
-                } else if (FAST) {
+                if (FAST) {
                     ld[k][e] = *(const f32x2 *)(src + off[k][e]);
                 } else {
                     ld[k][e][0] = *(const float *)(src + off[k][e]);
@@ -128,7 +126,7 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
                 rv[e][1] = (yok && xx + 1 >= 0 && xx + 1 < w) ? ld[k][e][1] : 0.0f;
                 if (relu_in) rv[e] = __builtin_elementwise_max(rv[e], f32x2{0.0f, 0.0f});
             }
-            if (iok && !((ABL & 8) && b > b_first)) {  // (ABL 8, timing only: the tile is staged for the first item alone)
+            if (iok) {
                 float *d = tile + (p * DW_LW + 2 * q) * 2;
                 *(f32x4 *)d = f32x4{rv[0][0], rv[1][0], rv[0][1], rv[1][1]};
                 *(f32x4 *)(d + DW_IMG) = f32x4{rv[1][0], rv[2][0], rv[1][1], rv[2][1]};
@@ -145,7 +143,7 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
 #pragma unroll
             for (int j = 0; j < 4; ++j) accA[j] = accB[j] = f32x2{0.0f, 0.0f};
 #pragma unroll
-            for (int m = 0; m < ((ABL & 1) ? 1 : DW_K + 2); ++m) {
+            for (int m = 0; m < DW_K + 2; ++m) {
                 // line m = input rows (4t + m, 4t + m + 1): pair 2t + m/2 of E (m even) or pair 2t + (m-1)/2 of O (m odd); it is
                 // kernel row m of output pair A and kernel row m - 2 of pair B.  Output column 4 tg + j, tap kx reads LDS column
                 // 4 tg + j + kx + 1 (LDS column 0 is image column x0 - 4): columns 4 tg .. 4 tg + 11 = three aligned b128
@@ -191,7 +189,6 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
                     const float o = fmaf((e < 2 ? accA[j][e] : accB[j][e - 2]) + bc, sc, sh);
                     r[j] = relu ? fmaxf(o, 0.0f) : o;
                 }
-                if ((ABL & 16) && r[0] != 12345.678f) continue;  // (ABL 16, timing only: no output stores)
                 if (FAST && x + 3 < w) {  // w even, plane 8-byte aligned: float2 stores are always aligned
 #pragma unroll
                     for (int j = 0; j < 4; j += 2) *(f32x2 *)(dst + j) = f32x2{r[j], r[j + 1]};
@@ -208,7 +205,7 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
     }
 }
 
-template <bool FAST, bool RELU_IN, bool RELU, int ABL = 0>
+template <bool FAST, bool RELU_IN, bool RELU>
 __global__ __launch_bounds__(256, FAST ? 4 : 3) void dwconv7x7_bn_relu_kernel(const float *__restrict__ in, int B, int C, int h, int w,
                                                                    const float *__restrict__ weight,
                                                                    const float *__restrict__ bias,
@@ -235,11 +232,11 @@ __global__ __launch_bounds__(256, FAST ? 4 : 3) void dwconv7x7_bn_relu_kernel(co
     if (tile_ < nstd) {
         const int ncol = nstd / nty;  // standard tile columns
         const int bx = tile_ % ncol, by = tile_ / ncol;
-        dw_tile<DwStd, FAST, RELU_IN, RELU, ABL>(tile, in, C, h, w, weight, bias, scale, shift, out, c, b_first, b_end, bx * DwStd::TX,
-                                                 by * DwStd::TY);
+        dw_tile<DwStd, FAST, RELU_IN, RELU>(tile, in, C, h, w, weight, bias, scale, shift, out, c, b_first, b_end, bx * DwStd::TX,
+                                            by * DwStd::TY);
     } else {
-        dw_tile<DwNarrow, FAST, RELU_IN, RELU, ABL>(tile, in, C, h, w, weight, bias, scale, shift, out, c, b_first, b_end,
-                                                    (nstd / nty) * DwStd::TX, (tile_ - nstd) * DwNarrow::TY);
+        dw_tile<DwNarrow, FAST, RELU_IN, RELU>(tile, in, C, h, w, weight, bias, scale, shift, out, c, b_first, b_end,
+                                               (nstd / nty) * DwStd::TX, (tile_ - nstd) * DwNarrow::TY);
     }
 }
 
@@ -536,7 +533,7 @@ __global__ __launch_bounds__(256) void conv1x1_x3_pack_kernel(const float *__res
 // NP = 3 ("split3", r4): three pieces per factor, SIX products per pair -- hi*hi + hi*mid + mid*hi + mid*mid + hi*lo + lo*hi, the
 // dropped ones (mid*lo, lo*mid, lo*lo) below 2^-24 of the product: fp32-class results (each product good to ~2^-23, the sum in
 // fp32) at 6/16 of the fp32 pipe's time.  24 KiB of weights per chunk: 64 KiB of LDS, two workgroups per CU.
-template <int ABL, int NP = 2>
+template <int NP = 2>
 __global__ __launch_bounds__(X3_NT, NP == 3 ? 2 : 3) void conv1x1_x3_kernel(const float *__restrict__ in, long in_bs, int Cin, long HW,
                                                               const char *__restrict__ wpk, const float *__restrict__ b2,
                                                               const float *__restrict__ add, int relu_out,
@@ -604,18 +601,9 @@ __global__ __launch_bounds__(X3_NT, NP == 3 ? 2 : 3) void conv1x1_x3_kernel(cons
 #define X3_MFMA(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x3_bf16x8, a_), __builtin_bit_cast(x3_bf16x8, b_), c_, 0, 0, 0)
     for (int c = 0; c < n; ++c) {
         const bool more = c + X3_NB - 1 < n;
-        if (more && !(ABL & 4)) dma(c + X3_NB - 1);  // (its slot was last read in iteration c - 1: everyone is past that barrier)
-        if (ABL & 2) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            continue;
-        }
+        if (more) dma(c + X3_NB - 1);  // (its slot was last read in iteration c - 1: everyone is past that barrier)
         const float *X = &xbuf[c % X3_NB][8 * (lane >> 5) * X3_P + wq * 64 + (lane & 31)];
         uint4 bh[2], bl[2], bm[NP == 3 ? 2 : 1];
-        if (ABL & 16) {
-#pragma unroll
-            for (int pb = 0; pb < 2; ++pb) bh[pb] = bl[pb] = make_uint4(lane + c, lane, c, pb);
-        } else {
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
             float v[8];
@@ -633,7 +621,6 @@ __global__ __launch_bounds__(X3_NT, NP == 3 ? 2 : 3) void conv1x1_x3_kernel(cons
                 x3_split(v[6], v[7], bh[pb].w, bl[pb].w);
             }
         }
-        }
         const uint4 *W = (const uint4 *)&wbuf[c % X3_NB][0] + (wc * 4) * 64 + lane;
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk) {
@@ -649,11 +636,6 @@ __global__ __launch_bounds__(X3_NT, NP == 3 ? 2 : 3) void conv1x1_x3_kernel(cons
                     X3_MFMA(am, bh[pb], acc[blk][pb]);
                     X3_MFMA(ah, bh[pb], acc[blk][pb]);
                 }
-                continue;
-            }
-            if (ABL & 8) {
-                acc[blk][0][0] += __uint_as_float((ah.x ^ bl[0].x ^ bh[0].y ^ bl[0].z ^ bh[0].w) & 0xff);
-                acc[blk][1][0] += __uint_as_float((al.x ^ bl[1].x ^ bh[1].y ^ bl[1].z ^ bh[1].w ^ bh[1].x ^ bl[1].y ^ bh[0].x ^ bl[0].y ^ bh[0].z ^ bl[0].w ^ bh[1].z ^ bl[1].w) & 0xff);
                 continue;
             }
 #pragma unroll
@@ -702,7 +684,7 @@ __global__ __launch_bounds__(X3_NT, NP == 3 ? 2 : 3) void conv1x1_x3_kernel(cons
 #pragma unroll
     for (int pb = 0; pb < 2; ++pb) {
         const long p = p0 + wq * 64 + pb * 32 + (lane & 31);
-        if (p >= HW || ((ABL & 1) && acc[0][pb][0] != 12345.0f)) continue;
+        if (p >= HW) continue;
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
@@ -750,15 +732,8 @@ template <int RW_KC>
 __global__ __launch_bounds__(RW_NT, 2) void conv1x1_rw_kernel(const float *__restrict__ in, long in_bs, int Cin, long HW,
                                                               const float *__restrict__ w2t, const float *__restrict__ b2,
                                                               int relu_out, float *__restrict__ out, int tpp, int total_tiles,
-                                                              int G, int halves, int abl_arg)
+                                                              int G, int halves, int /* always 0 */)
 {
-    // abl (-DMANET_ABLATION builds, timing only): 1 no output stores, 2 no barrier, 4 no DMA after the prologue, 8 no refills
-    // (a compile-time 0 otherwise: as a run-time value its tests put a scalar branch around every refill of the MFMA loop)
-#ifdef MANET_ABLATION
-    const int abl = abl_arg;
-#else
-    constexpr int abl = 0;
-#endif
     __shared__ __attribute__((aligned(1024))) float xbuf[RW_NB][RW_KC * RW_P];
     __shared__ float bsh[128];
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, kk = lane >> 5;
@@ -808,7 +783,7 @@ __global__ __launch_bounds__(RW_NT, 2) void conv1x1_rw_kernel(const float *__res
     if (last_p0 + lpix > HW - 4) lpix = HW - 4 - last_p0;
     const unsigned lane_off_last = (unsigned)(((long)(lane >> 4) * HW + lpix) * 4);
     auto issue = [&]() __attribute__((always_inline)) {
-        if (pf_left <= 0 || ((abl & 4) && issued >= RW_NB - 1)) return;  // (uniform)
+        if (pf_left <= 0) return;  // (uniform)
         // this wave's pieces: channel rows (RW_KC / 4) wave .. + RW_KC / 4 - 1 of the chunk, four rows (1 KiB) per piece
         const float *sbase = in + (long)pf_b * in_bs + (long)(pf_c * RW_KC + wave * (RW_KC / 4)) * HW + (long)pf_p * RW_P;
         const unsigned voff = (pf_p == tpp - 1) ? lane_off_last : lane_off;
@@ -869,21 +844,19 @@ __global__ __launch_bounds__(RW_NT, 2) void conv1x1_rw_kernel(const float *__res
                     if constexpr ((MODE & 2) != 0) acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ks], F1[f], first ? zero16 : acc[1][0], 0, 0, 0);
                     if constexpr ((MODE & 1) != 0) acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ks + 1], F0[f + 1], first ? zero16 : acc[0][1], 0, 0, 0);
                     if constexpr ((MODE & 2) != 0) acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[ks + 1], F1[f + 1], first ? zero16 : acc[1][1], 0, 0, 0);
-                    if (!(abl & 8)) {
-                        // k-steps s + 8, s + 9 of this stage, or of the next stage's first eight (a stale read behind the last step)
-                        const float *X = s + FH < RW_KC / 2 ? Xc + 2 * (s + FH) * RW_P : Xn + 2 * (s + FH - RW_KC / 2) * RW_P;
-                        const f32x2 va = *(const f32x2 *)X, vb = *(const f32x2 *)(X + 2 * RW_P);
-                        F0[f] = va[0];
-                        F1[f] = va[1];
-                        F0[f + 1] = vb[0];
-                        F1[f + 1] = vb[1];
-                    }
+                    // k-steps s + 8, s + 9 of this stage, or of the next stage's first eight (a stale read behind the last step)
+                    const float *X = s + FH < RW_KC / 2 ? Xc + 2 * (s + FH) * RW_P : Xn + 2 * (s + FH - RW_KC / 2) * RW_P;
+                    const f32x2 va = *(const f32x2 *)X, vb = *(const f32x2 *)(X + 2 * RW_P);
+                    F0[f] = va[0];
+                    F1[f] = va[1];
+                    F0[f + 1] = vb[0];
+                    F1[f + 1] = vb[1];
                     __builtin_amdgcn_sched_group_barrier(0x008, MODE == 3 ? 4 : 2, 0);  // the MFMAs
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // the refill (one ds_read2_b64) right behind them
                 }
                 rw_wait_vmcnt((RW_KC / 16) * (issued - 1 - (st + 2)));  // step st + 2 has landed: only the steps behind it may be out
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of stages st, st + 1 have returned
-                if (!(abl & 2)) __syncthreads();
+                __syncthreads();
                 ++st;
             }
         }
@@ -901,12 +874,12 @@ __global__ __launch_bounds__(RW_NT, 2) void conv1x1_rw_kernel(const float *__res
                     if constexpr (MODE == 3) {
                         f32x2 v = {(acc[0][0][r] + acc[0][1][r]) + bb, (acc[1][0][r] + acc[1][1][r]) + bb};
                         if (relu_out) v = __builtin_elementwise_max(v, f32x2{0.0f, 0.0f});
-                        if (!(abl & 1)) *(f32x2 *)((dst + (long)row * HW) + voff) = v;
+                        *(f32x2 *)((dst + (long)row * HW) + voff) = v;
                     } else {
                         constexpr int pb = MODE == 1 ? 0 : 1;
                         float v = (acc[pb][0][r] + acc[pb][1][r]) + bb;
                         if (relu_out) v = fmaxf(v, 0.0f);
-                        if (!(abl & 1)) (dst + (long)row * HW)[voff + pb] = v;
+                        (dst + (long)row * HW)[voff + pb] = v;
                     }
                 }
             }
@@ -1102,36 +1075,18 @@ extern "C" int manet_dwconv7x7_bn_relu_ex(const float *in, int B, int C, int h, 
     const long nblocks = 8L * ntile * ((planes + 7) / 8);  // (planes in groups of eight: one per XCD)
     if (nblocks > 0x7fffffffL) return manet_set_error(MANET_E_INVALID, "too many tiles for one launch");
     dim3 grid((unsigned)nblocks);
-#define DW_LAUNCH2(F_, RI_, R_, A_)                                                                                    \
-    hipLaunchKernelGGL((dwconv7x7_bn_relu_kernel<F_, RI_, R_, A_>), grid, dim3(256), 0, (hipStream_t)stream, in, B, C, h, w, weight, \
+#define DW_LAUNCH2(F_, RI_, R_)                                                                                        \
+    hipLaunchKernelGGL((dwconv7x7_bn_relu_kernel<F_, RI_, R_>), grid, dim3(256), 0, (hipStream_t)stream, in, B, C, h, w, weight, \
                        bias, bn_scale, bn_shift, out, per_item, ntx, nty, nstd, ntile)
-#define DW_LAUNCH(F_, A_)                                                                                              \
+#define DW_LAUNCH(F_)                                                                                                  \
     do {                                                                                                               \
-        if (relu_in && relu) DW_LAUNCH2(F_, true, true, A_);                                                           \
-        else if (relu_in) DW_LAUNCH2(F_, true, false, A_);                                                             \
-        else if (relu) DW_LAUNCH2(F_, false, true, A_);                                                                \
-        else DW_LAUNCH2(F_, false, false, A_);                                                                         \
+        if (relu_in && relu) DW_LAUNCH2(F_, true, true);                                                               \
+        else if (relu_in) DW_LAUNCH2(F_, true, false);                                                                 \
+        else if (relu) DW_LAUNCH2(F_, false, true);                                                                    \
+        else DW_LAUNCH2(F_, false, false);                                                                             \
     } while (0)
-    if (w % 2 == 0 && w >= 2 && ((size_t)in & 7) == 0 && ((size_t)out & 7) == 0) {
-#ifdef MANET_ABLATION
-        switch (manet_tune_get(MANET_TUNE_ABLATION, 0)) {  // timing experiments only (tools/pw_bench.py --dw)
-        case 1: DW_LAUNCH(true, 1); break;
-        case 2: DW_LAUNCH(true, 2); break;
-        case 3: DW_LAUNCH(true, 3); break;
-        case 4: DW_LAUNCH(true, 4); break;
-        case 8: DW_LAUNCH(true, 8); break;
-        case 12: DW_LAUNCH(true, 12); break;
-        case 14: DW_LAUNCH(true, 14); break;
-        case 16: DW_LAUNCH(true, 16); break;
-        case 18: DW_LAUNCH(true, 18); break;
-        case 30: DW_LAUNCH(true, 30); break;
-        default: DW_LAUNCH(true, 0);
-        }
-#else
-        DW_LAUNCH(true, 0);
-#endif
-    } else
-        DW_LAUNCH(false, 0);
+    if (w % 2 == 0 && w >= 2 && ((size_t)in & 7) == 0 && ((size_t)out & 7) == 0) DW_LAUNCH(true);
+    else DW_LAUNCH(false);
 #undef DW_LAUNCH2
 #undef DW_LAUNCH
     return manet_check_launch("manet_dwconv7x7_bn_relu_f32");
@@ -1183,15 +1138,8 @@ static int conv1x1_f32_impl(const float *in, int64_t in_batch_stride, int B, int
         const int tpp = (int)((HW + RW_P - 1) / RW_P);
         const long total = (long)tpp * B;
         int G = 256;  // pixel-range groups: one per CU; each is served by two workgroups (the output-channel halves)
-        if (manet_tune_get(MANET_TUNE_RW_GROUPS, 0) > 0) G = manet_tune_get(MANET_TUNE_RW_GROUPS, 0);
         if (total < G) G = (int)total;
-        const size_t rw_pad = (size_t)manet_tune_get(MANET_TUNE_RW_LDS_PAD, 0) * 1024;
         const unsigned blocks = (unsigned)(((G + 7) / 8) * 16);
-#ifdef MANET_ABLATION
-        const int rw_abl = manet_tune_get(MANET_TUNE_ABLATION, 0);
-#else
-        const int rw_abl = 0;
-#endif
         // ranges in half-tile units where that shortens the longest group by half a tile of at most ten (804 tiles on 256 groups:
         // 4 -> 3 1/2; 1 206: 5 either way, and two half tiles per group would only cost)
         const long per_whole = (total + G - 1) / G, per_half = (2 * total + G - 1) / G;
@@ -1200,11 +1148,11 @@ static int conv1x1_f32_impl(const float *in, int64_t in_batch_stride, int B, int
         if (tune == 3) halves = 0;  // (3 / 4: whole tiles / half-tile units everywhere, A/B timing and tests)
         if (tune == 4) halves = total >= G ? 1 : 0;
         if (Cin % 64 == 0 && tune != 2)  // (2: 32-channel stages everywhere, A/B timing)
-            hipLaunchKernelGGL(conv1x1_rw_kernel<64>, dim3(blocks), dim3(RW_NT), rw_pad, (hipStream_t)stream, in, (long)in_batch_stride, Cin,
-                               (long)HW, w2t, b2, relu_out, out, tpp, (int)total, G, halves, rw_abl);
+            hipLaunchKernelGGL(conv1x1_rw_kernel<64>, dim3(blocks), dim3(RW_NT), 0, (hipStream_t)stream, in, (long)in_batch_stride, Cin,
+                               (long)HW, w2t, b2, relu_out, out, tpp, (int)total, G, halves, 0);
         else
-            hipLaunchKernelGGL(conv1x1_rw_kernel<32>, dim3(blocks), dim3(RW_NT), rw_pad, (hipStream_t)stream, in, (long)in_batch_stride, Cin,
-                               (long)HW, w2t, b2, relu_out, out, tpp, (int)total, G, halves, rw_abl);
+            hipLaunchKernelGGL(conv1x1_rw_kernel<32>, dim3(blocks), dim3(RW_NT), 0, (hipStream_t)stream, in, (long)in_batch_stride, Cin,
+                               (long)HW, w2t, b2, relu_out, out, tpp, (int)total, G, halves, 0);
         return manet_check_launch("manet_conv1x1_f32 (resident weights)");
     }
     dim3 grid((unsigned)((HW + PW_P - 1) / PW_P), (unsigned)B);
@@ -1270,29 +1218,11 @@ static int x3_impl(const float *in, int64_t in_batch_stride, int B, int Cin, int
     if (head_w && add) return manet_set_error(MANET_E_INVALID, "add and the fused output layer are exclusive");
     dim3 grid((unsigned)((HW + X3_P - 1) / X3_P), (unsigned)B);
     if (pieces == 3) {
-        hipLaunchKernelGGL((conv1x1_x3_kernel<0, 3>), grid, dim3(X3_NT), 0, (hipStream_t)stream, in, (long)in_batch_stride, Cin, (long)HW,
+        hipLaunchKernelGGL(conv1x1_x3_kernel<3>, grid, dim3(X3_NT), 0, (hipStream_t)stream, in, (long)in_batch_stride, Cin, (long)HW,
                            (const char *)wpk, b2, add, relu_out, out, head_w, head_b, head_out);
         return manet_check_launch("manet_conv1x1_x6_f32");
     }
-#define X3_LAUNCH(A_)                                                                                                        \
-    hipLaunchKernelGGL(conv1x1_x3_kernel<A_>, grid, dim3(X3_NT), 0, (hipStream_t)stream, in, (long)in_batch_stride, Cin, (long)HW, \
-                       (const char *)wpk, b2, add, relu_out, out, head_w, head_b, head_out)
-#ifdef MANET_ABLATION
-    switch (manet_tune_get(MANET_TUNE_ABLATION, 0)) {  // timing experiments only (tools/pw_bench.py)
-    case 1: X3_LAUNCH(1); break;
-    case 2: X3_LAUNCH(2); break;
-    case 3: X3_LAUNCH(3); break;
-    case 4: X3_LAUNCH(4); break;
-    case 6: X3_LAUNCH(6); break;
-    case 7: X3_LAUNCH(7); break;
-    case 9: X3_LAUNCH(9); break;
-    case 17: X3_LAUNCH(17); break;
-    case 25: X3_LAUNCH(25); break;
-    default: X3_LAUNCH(0);
-    }
-#else
-    X3_LAUNCH(0);
-#endif
-#undef X3_LAUNCH
+    hipLaunchKernelGGL(conv1x1_x3_kernel<2>, grid, dim3(X3_NT), 0, (hipStream_t)stream, in, (long)in_batch_stride, Cin, (long)HW,
+                       (const char *)wpk, b2, add, relu_out, out, head_w, head_b, head_out);
     return manet_check_launch("manet_conv1x1_x3_f32");
 }

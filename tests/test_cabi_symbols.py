@@ -57,10 +57,22 @@ def test_argument_validation_without_a_gpu(built_lib):
     assert (oc.value, oh.value, ow.value) == (81, 20, 30)
 
 
+# the global_match_* / frame_prepare_* kernels of the library: one build, one set
+MATCH_KERNELS = sorted(
+    ["frame_prepare_kernel<%s, %s>" % (t, v) for t in ("float", "unsigned short") for v in ("false", "true")] +
+    ["global_match_f32_kernel<%d, %s>" % (ks, form) for ks in (16, 50, 52, 64)
+     for form in ("1, true, false", "1, true, true", "8, false, false")] +
+    ["global_match_f32_pipe_kernel<%d, %s>" % (ks, r) for ks in (16, 50, 52, 64) for r in ("false", "true")] +
+    ["global_match_bf16_wide_kernel<%d, %s>" % (k, f) for k in (2, 7) for f in ("false", "true")] +
+    ["global_match_bf16_pipe_kernel<9>"] +
+    ["global_match_bf16x3_kernel<%d>" % k for k in (2, 7, 9)] +
+    ["global_match_backward_kernel"])
+
+
 def test_default_build_carries_no_ablation_variants(built_lib):
-    """VERDICT r3 hygiene: the default build compiles only the kernels the data path can reach.  The tuning keys that select
-    variant / ablation instantiations are refused (with the rebuild recipe) unless the library was built with
-    -DMANET_ABLATION; the keys that only steer the shipped kernels (block map, split count, the unfused local route) work."""
+    """VERDICT r3 hygiene: the library compiles only the kernels the data path can reach.  The tuning keys that selected
+    variant / ablation instantiations and experiment launch forms are retired and refused by name; the keys that only steer the
+    shipped kernels (block map, split count, the unfused local route) work."""
     import subprocess as sp
     import sys
     code = (
@@ -69,18 +81,20 @@ def test_default_build_carries_no_ablation_variants(built_lib):
         "lib = _lib.load()\n"
         "assert lib.manet_tune_set(0, 4) == 0 and lib.manet_tune_set(0, -2**31) == 0\n"
         "assert lib.manet_tune_set(1, 16) == 0 and lib.manet_tune_set(1, -2**31) == 0\n"
-        "res = [lib.manet_tune_set(k, 1) for k in (2, 3, 5, 6)]\n"
-        "msg = lib.manet_last_error_string().decode()\n"
-        "print(res, msg)\n" % ROOT)
+        "for k in (2, 3, 5, 6, 7, 9, 11, 12):\n"
+        "    print('key', k, lib.manet_tune_set(k, 1), lib.manet_last_error_string().decode())\n" % ROOT)
     out = sp.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
+    lines = [l for l in out.stdout.splitlines() if l.startswith("key ")]
+    assert len(lines) == 8
+    for k, line in zip((2, 3, 5, 6, 7, 9, 11, 12), lines):
+        assert line.startswith("key %d -1 " % k), line
+        assert "tune key %d " % k in line and "removed" in line, line
     nm = sp.run(["nm", "-C", "--defined-only", built_lib], capture_output=True, text=True).stdout
-    ablation_build = "global_match_bf16_wide_kernel<7, 15" in nm
-    if ablation_build:
-        assert "[0, 0, 0, 0]" in out.stdout
-    else:
-        assert "[-1, -1, -1, -1]" in out.stdout and "MANET_ABLATION" in out.stdout
-        # none of the spilled / unreachable instantiations r3's build carried
-        for sym in ("global_match_bf16_wide_kernel<9", "global_match_bf16_wide_kernel<7, 4", "global_match_bf16_kernel<9, true, 2",
-                    "global_match_f32_kernel<64, 1, false>", "frame_prepare_kernel<float, 64>"):
-            assert sym not in nm, sym
+    # none of the spilled / unreachable instantiations r3's build carried: no wide kernel at k-step 9, no 64-column frame prepare,
+    # no un-pipelined k = 1 fp32 kernel, no ablation or register-staging form of the bf16 kernels
+    for sym in ("global_match_bf16_wide_kernel<9", "global_match_bf16_wide_kernel<7, 4", "global_match_bf16_kernel<",
+                "global_match_f32_kernel<64, 1, false", "frame_prepare_kernel<float, 64", "refine_debug_kernel"):
+        assert sym not in nm, sym
+    have = sorted(set(re.findall(r"__device_stub__((?:global_match_|frame_prepare_)\w+(?:<[^>]*>)?)\(", nm)))
+    assert have == MATCH_KERNELS, (sorted(set(have) - set(MATCH_KERNELS)), sorted(set(MATCH_KERNELS) - set(have)))

@@ -66,22 +66,22 @@ HOT = {
     # the headline fp32 global match at C = 100 (13 k-groups: KS = 50) and its arg-min twin; the bf16 kernel of configs[2] / [4]
     "global_match_f32_pipe_kernel<50, false>": (256, 2),
     "global_match_f32_pipe_kernel<50, true>": (256, 2),
-    "global_match_bf16_wide_kernel<7, 0, false>": (256, 2),
+    "global_match_bf16_wide_kernel<7, false>": (256, 2),
     "global_finish_kernel": (128, 4),
     # per-frame operands (the staging forms 480p / 720p clips take)
-    "frame_prepare_kernel<float, 32, true>": (128, 4),
-    "frame_prepare_kernel<unsigned short, 32, true>": (128, 4),
+    "frame_prepare_kernel<float, true>": (128, 4),
+    "frame_prepare_kernel<unsigned short, true>": (128, 4),
     # local window: the fused kernel and its two halves (stored volumes, r6), the reference's window radius and configs[2]'s
     "local_fused_kernel<12, 0>": (256, 2), "local_fused_kernel<12, 1>": (256, 2), "local_fused_kernel<12, 2>": (128, 4),
     "local_fused_kernel<4, 0>": (128, 4), "local_fused_kernel<4, 1>": (128, 4), "local_fused_kernel<4, 2>": (128, 4),
     # the head
-    "dwconv7x7_bn_relu_kernel<true, false, true, 0>": (128, 4),
-    "dwconv7x7_bn_relu_kernel<false, false, true, 0>": (168, 3),
+    "dwconv7x7_bn_relu_kernel<true, false, true>": (128, 4),
+    "dwconv7x7_bn_relu_kernel<false, false, true>": (168, 3),
     "conv1x1_rw_kernel<64>": (256, 2), "conv1x1_rw_kernel<32>": (256, 2),
     "conv1x1_mfma_kernel": (168, 3),
     "head_layer1_object_kernel<1>": (128, 4), "head_layer1_object_kernel<2>": (128, 4),
     "relu_conv1x1_c1_kernel": (128, 4),
-    "conv1x1_x3_kernel<0, 2>": (168, 3), "conv1x1_x3_kernel<0, 3>": (256, 2),
+    "conv1x1_x3_kernel<2>": (168, 3), "conv1x1_x3_kernel<3>": (256, 2),
     # the mask step
     "upsample_argmax_kernel": (128, 4), "frame_begin_kernel": (128, 4),
 }
@@ -109,9 +109,9 @@ def test_every_window_radius_of_the_local_kernels_is_spill_free(resources):
 
 def test_no_kernel_of_the_library_spills_vector_registers_except_the_known_one(resources):
     """Anything else that starts spilling shows up here.  Known and accepted: the bf16r filter's arg variant (one VGPR, 8 bytes:
-    global_match_bf16_wide_kernel<7, 0, true>, off the timed paths of the headline) and the SGPR-spill bookkeeping of the
+    global_match_bf16_wide_kernel<7, true>, off the timed paths of the headline) and the SGPR-spill bookkeeping of the
     generic-stride fp32 frame prepare (36 bytes reserved, no scratch instruction in its code; odd widths / strided views only)."""
-    known = {"global_match_bf16_wide_kernel<7, 0, true>", "frame_prepare_kernel<float, 32, false>"}
+    known = {"global_match_bf16_wide_kernel<7, true>", "frame_prepare_kernel<float, false>"}
     bad = {k: v for k, v in resources.items()
            if (v.get("VGPRs Spill", 0) or v.get("ScratchSize [bytes/lane]", 0)) and k not in known}
     assert not bad, bad

@@ -43,22 +43,17 @@ def kernel_us(lib, fn, channel, n=40):
 
 
 def main():
-    os.environ["MANET_TUNING"] = "1"
     lib = _lib.load()
     for (h, w, d, compute, st) in ((120, 214, 12, "f32", torch.float32), (120, 214, 4, "bf16", torch.bfloat16),
                                    (180, 320, 4, "bf16", torch.bfloat16), (120, 214, 4, "f32", torch.bfloat16)):
         e = (torch.relu(torch.randn(2, 100, h, w, device="cuda")) * 0.1).to(st)
         lab = torch.zeros(h, w, dtype=torch.int32, device="cuda")
-        for xc in (0, 1):
-            if lib.manet_tune_set(6, xc) != 0:  # (the 64-column variant lives in -DMANET_ABLATION builds only)
-                if xc:
-                    continue
-            t_prep = timeit(lambda: ops.prepare_frames(e[0], compute=compute, max_distance=d))
-            t_prep_nopool = timeit(lambda: ops.prepare_frames(e[0], compute=compute, max_distance=-1))
-            k_prep = kernel_us(lib, lambda: ops.prepare_frames(e[0], compute=compute, max_distance=d), 2)
-            k_nopool = kernel_us(lib, lambda: ops.prepare_frames(e[0], compute=compute, max_distance=-1), 2)
-            print("%dx%d d=%d %s/%s XC=%d: frame_prepare KERNEL %.1f us (image only %.1f us); python loop %.1f / %.1f us per call"
-                  % (h, w, d, compute, st, 64 if xc else 32, k_prep, k_nopool, t_prep, t_prep_nopool))
+        t_prep = timeit(lambda: ops.prepare_frames(e[0], compute=compute, max_distance=d))
+        t_prep_nopool = timeit(lambda: ops.prepare_frames(e[0], compute=compute, max_distance=-1))
+        k_prep = kernel_us(lib, lambda: ops.prepare_frames(e[0], compute=compute, max_distance=d), 2)
+        k_nopool = kernel_us(lib, lambda: ops.prepare_frames(e[0], compute=compute, max_distance=-1), 2)
+        print("%dx%d d=%d %s/%s: frame_prepare KERNEL %.1f us (image only %.1f us); python loop %.1f / %.1f us per call"
+              % (h, w, d, compute, st, k_prep, k_nopool, t_prep, t_prep_nopool))
         t_pack = timeit(lambda: ops.PackedQuery(e[0].permute(1, 2, 0), compute=compute))
         fr = ops.prepare_frames(e, compute=compute, max_distance=d)
         t_old = timeit(lambda: ops.local_match(e[0].permute(1, 2, 0), e[1].permute(1, 2, 0), lab, 2, d))
