@@ -171,10 +171,9 @@ class GlobalMatchTopkFn(torch.autograd.Function):
             return None, None, None, None, None
         g = grad_out.contiguous().float()
         gq_sum = gr_sum = None
-        for j in range(ctx.k):  # contiguous per-rank gradients, summed with torch
+        for j in range(ctx.k):  # per-rank gradients in the inputs' own memory order (as for k = 1), summed with torch
             gj = (g * wgt[j]).contiguous()
-            gq = torch.empty(qry.shape, dtype=torch.float32, device=qry.device) if need_qry else None
-            gr = torch.empty(ref.shape, dtype=torch.float32, device=qry.device) if need_ref else None
+            gq, gr = _grad_like(qry, need_qry), _grad_like(ref, need_ref)
             _global_backward_call(ref, qry, arg[j], gj, ctx.n_ids, gq, gr)
             if need_qry:
                 gq_sum = gq if gq_sum is None else gq_sum.add_(gq)

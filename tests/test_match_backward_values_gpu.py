@@ -1,0 +1,403 @@
+"""GPU: the VALUES of the matching path's backward, both routes -- the float-atomic kernels (csrc/global_match.hip,
+csrc/local_match.hip) and the ordered, atomic-free ones (csrc/match_train.hip) -- against the float64 restatements of
+tests/match_grad_ref.py (held to the reference's own autograd by tests/test_match_grad_ref.py), at the shapes where a kernel
+can be wrong with the same bits on every run.  Every case runs deterministic=False and deterministic=True through
+ops.global_match / ops.local_match and takes the selection from the op's saved tensors.
+
+(a) exact arithmetic: global k in {1, 2, 4, 8} and the local match without downsample.  Embeddings are multiples of 2^-4 in
+    [0, 2), grad_out multiples of 2^-2 in [-1, 1] with |g| >= 1/2, the rank weights of a power-of-two k are dyadic: every term
+    2 gw (q - k) is a multiple of 2^-8 bounded by 4 and a sum of fewer than 2^24 / (4 * 2^8) = 16 384 of them is exact in fp32
+    in ANY order -- both routes must return the float64 gradient bit for bit.  Each case asserts that budget from the recorded
+    selection before it compares, and that the recorded selection has the object's label and attains the brute-force minimum
+    (ties are harmless: the restatement uses the recorded rows).  Each case runs C-major and row-major (same values, the
+    gradient in the input's strides) and once with either operand frozen (the same bits; None on the ordered route).
+      group splitting (one workgroup lists 2400 > MT_LCAP hits), two epochs of the scan (134 400 entries: replaced ranks, -1
+      entries, the farthest-neighbour share, an object without rows), ROWS = 32 with a one-row last workgroup (M0 = 16 641),
+      N = 1 / C = 1, C in {63, 64, 65, 128}, 64 ids, labels -1 and >= n_ids; local (h, w, C, d, n_ids) = (1, 1, 1, 0, 1),
+      (3, 5, 5, 1, 2), (9, 11, 65, 12, 3), (17, 33, 128, 4, 9)
+(b) tolerance: the local match with downsample (sigmoid, bilinear weights) and global k in {3, 5} (1/3 weights) cannot be exact.
+    error = max |got - want64| / max |want64| per tensor (rel_err of tests/test_match_train_gpu.py), bound 2e-5: the project's
+    tolerance for the gradient fixtures (atol = 2e-5 * scale), which already holds both routes to the reference's autograd.
+    Largest error measured on the MI355X per group, atomic / ordered route (previous or bank, current or query):
+      global, group-splitting shape, k = 3 and 5   bank 1.9e-6 / 1.7e-6, query 1.3e-7 / 1.3e-7
+      local, 16 seeded shapes                      previous 3.7e-7 / 3.8e-7, current 2.8e-7 / 2.5e-7
+      local, cover-limited lists (7 x 9, d = 4)    previous 1.2e-7, current 8.6e-8, the same figure on both routes
+      local, colliding 52 x 60, d = 12             previous 6.6e-6, current 5.7e-6, the same figure on both routes
+      local, 40 sparse ids                         previous 1.3e-7 / 1.6e-7, current 1.6e-7 / 1.7e-7
+    (no case needed another bound than 2e-5.)
+"""
+import numpy as np
+import pytest
+import torch
+
+import match_grad_ref as R
+from test_match_train_gpu import colliding, rel_err, saved
+
+pytestmark = pytest.mark.gpu
+BOUND = 2e-5
+QUANTUM, BITS = 2.0 ** -8, 2 ** 24
+MT_LCAP, MT_EPOCH = 1024, 512 * 256  # csrc/match_train.hip: list entries in LDS; entries per epoch of the scan
+ROUTES = [("atomic", False), ("ordered", True)]
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    from cvpr2020_manet_amd import ops as o
+    return o
+
+
+def gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def grid(shape, g, lo=0, hi=32):
+    """multiples of 2^-4 in [lo / 16, hi / 16)"""
+    return torch.randint(lo, hi, shape, generator=g).float() / 16
+
+
+def grid_gout(shape, g):
+    """multiples of 2^-2 in [-1, 1] with |g| >= 1/2"""
+    return torch.tensor([-1.0, -0.75, -0.5, 0.5, 0.75, 1.0])[torch.randint(0, 6, shape, generator=g)].cuda()
+
+
+def leaf(chw, layout, grad=True):
+    """a leaf in the given memory order -> (leaf, its [h, w, C] view for the op, leaf-shaped gradient -> [C, h, w])"""
+    if layout == "cmajor":  # [C, h, w].permute(1, 2, 0), as the heads write embeddings
+        t = chw.clone().contiguous().requires_grad_(grad)
+        return t, t.permute(1, 2, 0), lambda g: g
+    t = chw.permute(1, 2, 0).contiguous().requires_grad_(grad)
+    return t, t, lambda g: g.permute(2, 0, 1)
+
+
+def same_strides(g, t):
+    return all(a == b for a, b, n in zip(g.stride(), t.stride(), t.shape) if n > 1)
+
+
+# ------------------------------------------------------------------------------------------------------------------ global
+
+def run_global(ops, ref, qry, lab, n_ids, k, gout, det, layout, frozen=None):
+    """-> (arg [k, N, n_ids], wgt [k, N, n_ids], grad_ref [C, ., .] or None, grad_qry or None)"""
+    r, rv, rback = leaf(ref, layout, frozen != "ref")
+    q, qv, qback = leaf(qry, layout, frozen != "qry")
+    out = ops.global_match(rv, qv, lab, n_ids, k_nearest_neighbors=k, deterministic=det)
+    arg = saved(out)[0]
+    if k == 1:
+        arg, wgt = arg[None], torch.ones_like(out)[None]
+    else:
+        wgt = [t for t in saved(out, torch.float32) if t.shape == arg.shape][0]
+    if frozen is not None:
+        raw = out.grad_fn.apply(*((gout, None) if k == 1 else (gout,)))  # the node's own return values
+        if det:
+            assert raw[0 if frozen == "ref" else 1] is None
+        assert raw[1 if frozen == "ref" else 0] is not None
+    wanted = [t for t in (r, q) if t.requires_grad]
+    grads = list(torch.autograd.grad(out, wanted, gout))
+    for g_, t in zip(grads, wanted):
+        assert same_strides(g_, t), (g_.stride(), t.stride(), layout)
+    gr = rback(grads.pop(0)) if r.requires_grad else None
+    gq = qback(grads.pop(0)) if q.requires_grad else None
+    return arg, wgt, gr, gq
+
+
+def check_global_selection(ref, qry, lab, n_ids, k, arg):
+    """every recorded row has the object's label, no row twice, -1 exactly past the object's row count, and the recorded rows'
+    distances are the k smallest of the brute force (exact on the dyadic grid)"""
+    _, _, want_d, _ = R.global_select64(ref, qry, lab, n_ids, k)
+    dist = R.pairwise64(R.rows_of(qry.double()), R.rows_of(ref.double()))
+    a = arg.long()
+    valid = a >= 0
+    assert torch.equal(valid, torch.isfinite(want_d))  # (ascending: the real neighbours first)
+    objects = torch.arange(n_ids, device=a.device)[None, None, :].expand_as(a)
+    assert bool((lab.reshape(-1).long()[a.clamp(min=0)] == objects)[valid].all())
+    n_idx = torch.arange(a.shape[1], device=a.device)[None, :, None].expand_as(a)
+    got_d = torch.where(valid, dist[n_idx, a.clamp(min=0)], torch.full_like(want_d, float("inf")))
+    assert torch.equal(got_d.sort(0).values, want_d)
+    s = a.sort(0).values
+    assert not bool(((s[1:] == s[:-1]) & (s[1:] >= 0)).any())
+
+
+def exact_global(ops, ref, qry, lab, n_ids, k, seed):
+    """all runs of one exact case -> (arg, wgt) for the caller's path assertions"""
+    N = qry.shape[1] * qry.shape[2]
+    gout = grid_gout((N, n_ids), gen(seed))
+    arg0 = want = None
+    for name, det in ROUTES:
+        for layout, frozen in (("cmajor", None), ("rowmajor", None), ("cmajor", "ref"), ("rowmajor", "qry")):
+            arg, wgt, gr, gq = run_global(ops, ref, qry, lab, n_ids, k, gout, det, layout, frozen)
+            if arg0 is None:
+                arg0, wgt0 = arg, wgt
+                check_global_selection(ref, qry, lab, n_ids, k, arg)
+                # the bit budget: (most entries on one bank row or one query) x (largest |term|) / quantum < 2^24
+                rows = arg[arg >= 0].long()
+                most = max(int(torch.bincount(rows).max()) if rows.numel() else 0, k * n_ids)
+                spread = float(max(ref.max(), qry.max()) - min(ref.min(), qry.min()))
+                term = 2.0 * float((gout.abs()[None] * wgt).max()) * spread
+                assert term <= 4.0 and most * term / QUANTUM < BITS, (most, term)
+                want = R.global64(ref, qry, arg, wgt, gout)
+            assert torch.equal(arg, arg0) and torch.equal(wgt, wgt0)  # one selection for every run: one float64 reference
+            if gr is not None:
+                assert torch.equal(gr.double(), want[0]), (name, layout, frozen, "bank", rel_err(gr, want[0]))
+            if gq is not None:
+                assert torch.equal(gq.double(), want[1]), (name, layout, frozen, "query", rel_err(gq, want[1]))
+    assert float(want[0].abs().max()) > 0 and (N == 1 or float(want[1].abs().max()) > 0)
+    return arg0, wgt0
+
+
+def near_base(C, hq, wq, hb, wb, lab, n_ids, g, exact=True):
+    """every query nearest to ONE bank row per object: that row equals a base vector (+ 2^-4 in one channel per object), the
+    queries are near the base and every other row is far.  exact: on the dyadic grid; else continuous"""
+    if exact:
+        base = grid((C, 1, 1), g, 4, 12)
+        qry = base + grid((C, hq, wq), g, 0, 3)
+        ref = grid((C, hb, wb), g, 20, 32)
+    else:
+        base = torch.relu(torch.randn(C, 1, 1, generator=g)) * 0.1
+        qry = base + 0.003 * torch.randn(C, hq, wq, generator=g)
+        ref = base + 1.0 + torch.rand(C, hb, wb, generator=g)
+    for o in range(n_ids):
+        ys, xs = torch.nonzero(lab == o, as_tuple=True)
+        if len(ys):
+            ref[:, ys[len(ys) // 2], xs[len(xs) // 2]] = base[:, 0, 0]
+            ref[o % C, ys[len(ys) // 2], xs[len(xs) // 2]] += (1.0 / 16 if exact else 0.001 * o)
+    return ref.cuda(), qry.cuda()
+
+
+def test_global_exact_group_splitting(ops):
+    """N = 48 x 50 queries on a 20 x 20 bank, C = 33, 3 ids, k = 1: each of three workgroups lists 2400 > MT_LCAP hits"""
+    g = gen(100)
+    lab = torch.randint(0, 3, (20, 20), generator=g).int()
+    ref, qry = near_base(33, 48, 50, 20, 20, lab, 3, g)
+    arg, _ = exact_global(ops, ref, qry, lab.cuda(), 3, 1, 101)
+    assert int(torch.bincount(arg[arg >= 0].long()).max()) > MT_LCAP
+
+
+def test_global_exact_two_epochs_and_rank_changes(ops):
+    """the same queries, 7 ids, k = 8: 134 400 entries (two epochs of the scan); object 4 has one row and object 5 three
+    (replaced ranks: -1 entries and the farthest-neighbour share), object 6 none; labels -1 and >= n_ids in the bank"""
+    g = gen(110)
+    lab = torch.randint(0, 4, (20, 20), generator=g).int()
+    lab[3, 4] = 4
+    lab[5, 6], lab[5, 7], lab[19, 19] = 5, 5, 5
+    lab[0, 0], lab[10, 10], lab[11, 3], lab[12, 12] = -1, -1, 7, 9
+    ref, qry = near_base(33, 48, 50, 20, 20, lab, 7, g)
+    arg, wgt = exact_global(ops, ref, qry, lab.cuda(), 7, 8, 111)
+    assert arg.numel() > MT_EPOCH
+    assert int(torch.bincount(arg[arg >= 0].long()).max()) > MT_LCAP
+    assert bool((arg[:, :, 6] == -1).all()) and bool((wgt[:, :, 6] == 0).all())
+    assert int((arg[:, :, 4] >= 0).sum()) == 48 * 50 and int((arg[:, :, 5] >= 0).sum()) == 3 * 48 * 50
+    assert float(wgt[:, :, 4].max()) == 1.0 and float(wgt[:, :, 5].max()) == 0.75  # 1/8 + the replaced entries' 7/8, 5/8
+    assert bool((arg[:, :, :4] >= 0).all())
+
+
+@pytest.mark.parametrize("k", [1, 2])
+def test_global_exact_rows32_with_a_ragged_last_workgroup(ops, k):
+    """bank 129 x 129 = 16 641 rows > 16 384: the ROWS = 32 instantiation, whose last workgroup has ONE row -- selected here"""
+    g = gen(120 + k)
+    ref, qry = grid((8, 129, 129), g), grid((8, 37, 19), g)
+    lab = torch.randint(-1, 2, (129, 129), generator=g).int()
+    ref[:, -1, -1], lab[-1, -1] = qry[:, 0, 0], 0
+    arg, _ = exact_global(ops, ref.cuda(), qry.cuda(), lab.cuda(), 2, k, 122)
+    M0 = 129 * 129
+    assert M0 > 16384 and M0 % 32 == 1 and bool((arg == M0 - 1).any())
+
+
+@pytest.mark.parametrize("k", [1, 2, 4, 8])
+def test_global_exact_one_query_one_channel(ops, k):
+    ref = ((2 * torch.arange(17) + 1) % 32).float().reshape(1, 17, 1) / 16  # odd numerators: no row equals the query
+    qry = torch.ones(1, 1, 1)
+    lab = torch.tensor([0, 1, 1, 0, 1, -1, 1, 1, 0, 2, 1, 1, 1, 0, 1, 1, 1], dtype=torch.int32).reshape(17, 1)
+    exact_global(ops, ref.cuda(), qry.cuda(), lab.cuda(), 2, k, 131)
+
+
+@pytest.mark.parametrize("k", [1, 2, 4, 8])
+@pytest.mark.parametrize("C", [63, 64, 65, 128])
+def test_global_exact_ragged_small(ops, C, k):
+    """N = 33 x 7, M0 = 5 x 7 (three workgroups, the last with 3 rows), labels -1 .. n_ids + 1"""
+    g = gen(140 + C + k)
+    ref, qry = grid((C, 5, 7), g), grid((C, 33, 7), g)
+    lab = torch.randint(-1, 6, (5, 7), generator=g).int()
+    lab[0, 0], lab[0, 1] = -1, 5
+    arg, _ = exact_global(ops, ref.cuda(), qry.cuda(), lab.cuda(), 4, k, 141)
+    assert bool((lab == -1).any()) and bool((lab >= 4).any()) and bool((arg >= 0).any())
+
+
+@pytest.mark.parametrize("k", [1, 4])
+def test_global_exact_64_ids_most_of_them_empty(ops, k):
+    g = gen(150 + k)
+    ref, qry = grid((16, 5, 7), g), grid((16, 33, 7), g)
+    lab = torch.tensor([0, 3, 17, 40, 63], dtype=torch.int32)[torch.randint(0, 5, (5, 7), generator=g)]
+    arg, _ = exact_global(ops, ref.cuda(), qry.cuda(), lab.cuda(), 64, k, 151)
+    assert int((arg >= 0).any(0).any(0).sum()) == len(torch.unique(lab)) < 6
+
+
+@pytest.mark.parametrize("k,layout", [(3, "cmajor"), (5, "rowmajor")])
+def test_global_tolerance_group_splitting(ops, k, layout):
+    """the group-splitting shape with continuous inputs and the 1/3, 1/5 weights"""
+    g = gen(160 + k)
+    lab = torch.randint(0, 3, (20, 20), generator=g).int()
+    ref, qry = near_base(33, 48, 50, 20, 20, lab, 3, g, exact=False)
+    gout = torch.randn(48 * 50, 3, generator=g).cuda()
+    for name, det in ROUTES:
+        arg, wgt, gr, gq = run_global(ops, ref, qry, lab.cuda(), 3, k, gout, det, layout)
+        assert int(torch.bincount(arg[arg >= 0].long()).max()) > MT_LCAP
+        want = R.global64(ref, qry, arg, wgt, gout)
+        errs = (rel_err(gr, want[0]), rel_err(gq, want[1]))
+        print("global split k=%d %s %s: (bank, query) %.3e %.3e" % ((k, layout, name) + errs))
+        assert float(gr.abs().max()) > 0 and float(gq.abs().max()) > 0
+        assert max(errs) < BOUND, (name, errs)
+
+
+# ------------------------------------------------------------------------------------------------------------------- local
+
+def run_local(ops, prev, cur, lab, n_ids, d, downsample, gout, det, layout, frozen=None):
+    """-> (arg [h, w, n_ids], grad_prev [C, h, w] or None, grad_cur or None)"""
+    p, pv, pback = leaf(prev, layout, frozen != "prev")
+    c, cv, cback = leaf(cur, layout, frozen != "cur")
+    out = ops.local_match(pv, cv, lab, n_ids, d, downsample=downsample, deterministic=det)
+    arg = saved(out)[0]
+    if frozen is not None:
+        raw = out.grad_fn.apply(gout)
+        if det:
+            assert raw[0 if frozen == "prev" else 1] is None
+        assert raw[1 if frozen == "prev" else 0] is not None
+    wanted = [t for t in (p, c) if t.requires_grad]
+    grads = list(torch.autograd.grad(out, wanted, gout))
+    if downsample:  # (without downsample the backward works on C-major planes: the gradient comes C-major)
+        for g_, t in zip(grads, wanted):
+            assert same_strides(g_, t), (g_.stride(), t.stride(), layout)
+    gp = pback(grads.pop(0)) if p.requires_grad else None
+    gc = cback(grads.pop(0)) if c.requires_grad else None
+    return arg, gp, gc
+
+
+def exact_local_inputs(h, w, C, n_ids, seed):
+    """cur = a base vector + sparse 2^-4 noise, prev = cur + sparse noise in {-2^-4, 0, 2^-4}: every distance of the window
+    stays well below the constant 1.0, so the winners spread over the offsets"""
+    g = gen(seed)
+    sparse = lambda: (torch.rand(C, h, w, generator=g) < min(1.0, 8.0 / C)).float()
+    cur = grid((C, 1, 1), g, 4, 28) + sparse() * grid((C, h, w), g, 0, 2)
+    prev = cur + sparse() * grid((C, h, w), g, -1, 2)
+    prev[0, 0, 0] = cur[0, 0, 0] + 1.0 / 16  # (a non-zero difference whatever the noise drew)
+    lab = torch.randint(-1, n_ids, (h, w), generator=g).int()
+    lab[0, 0] = 0
+    return prev.cuda(), cur.cuda(), lab.cuda()
+
+
+@pytest.mark.parametrize("shape", [(1, 1, 1, 0, 1), (3, 5, 5, 1, 2), (9, 11, 65, 12, 3), (17, 33, 128, 4, 9)])
+def test_local_full_exact(ops, shape):
+    h, w, C, d, n_ids = shape
+    prev, cur, lab = exact_local_inputs(h, w, C, n_ids, 200 + h)
+    assert h * w == 1 or bool((lab == -1).any())
+    gout = grid_gout((h, w, n_ids), gen(201))
+    P = 2 * d + 1
+    arg0 = want = None
+    for name, det in ROUTES:
+        for layout, frozen in (("cmajor", None), ("rowmajor", None), ("cmajor", "prev"), ("rowmajor", "cur")):
+            arg, gp, gc = run_local(ops, prev, cur, lab, n_ids, d, False, gout, det, layout, frozen)
+            if arg0 is None:
+                arg0 = arg
+                ys, xs, os_ = torch.nonzero(arg >= 0, as_tuple=True)
+                assert len(ys) > 0
+                l = arg[ys, xs, os_].long()
+                # the recorded offsets carry the object's label (gathered at stride 2, 0 outside) and attain the brute-force minimum
+                yy, xx = ys + 2 * (l // P - d), xs + 2 * (l % P - d)
+                inside = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
+                seen = torch.where(inside, lab[yy.clamp(0, h - 1), xx.clamp(0, w - 1)].long(), torch.zeros_like(yy))
+                assert torch.equal(seen, os_)
+                brute, _ = R.local_select64(prev, cur, lab, n_ids, d, False)
+                assert torch.equal(R.local_out64(prev.double(), cur.double(), arg, d, False),
+                                   R.local_out64(prev.double(), cur.double(), brute, d, False))
+                # the bit budget: most terms on one previous-frame pixel (or one current-frame pixel) x 4 / 2^-8 < 2^24
+                target = (ys + l // P - d) * w + xs + l % P - d
+                most = max(int(torch.bincount(target).max()), n_ids)
+                spread = float(max(prev.max(), cur.max()) - min(prev.min(), cur.min()))
+                assert 2.0 * spread <= 4.0 and most * 4.0 / QUANTUM < BITS
+                want = R.local64(prev, cur, arg, gout, d, False)
+                if h * w > 1:
+                    assert len(torch.unique(l)) > 1  # more than the centre offset
+            assert torch.equal(arg, arg0)
+            if gp is not None:
+                assert torch.equal(gp.double(), want[0]), (name, layout, frozen, "prev", rel_err(gp, want[0]))
+            if gc is not None:
+                assert torch.equal(gc.double(), want[1]), (name, layout, frozen, "cur", rel_err(gc, want[1]))
+    assert float(want[0].abs().max()) > 0 and float(want[1].abs().max()) > 0
+
+
+def tolerance_local(ops, tag, prev, cur, lab, n_ids, d, gout, layout):
+    """both routes of the downsample configuration against the float64 restatement on the recorded offsets -> the winners"""
+    h, w = lab.shape
+    for name, det in ROUTES:
+        arg, gp, gc = run_local(ops, prev, cur, lab, n_ids, d, True, gout, det, layout)
+        winners = int((arg >= 0).sum())
+        assert winners > 0
+        want = R.local64(prev, cur, arg, gout, d, True)
+        errs = (rel_err(gp, want[0]), rel_err(gc, want[1]))
+        print("local %s [%d,%d,%d] d=%d ids=%d %s %s: %d winners, (prev, cur) %.3e %.3e" % (
+            (tag, cur.shape[0], h, w, d, n_ids, layout, name, winners) + errs))
+        assert float(gp.abs().max()) > 0 and float(gc.abs().max()) > 0
+        if h % 2:  # the 2x2 mean drops an odd last row / column: gradient 0, and written
+            assert not bool(gp[:, -1].any()) and not bool(gc[:, -1].any())
+        if w % 2:
+            assert not bool(gp[:, :, -1].any()) and not bool(gc[:, :, -1].any())
+        assert max(errs) < BOUND, (name, errs)
+    return arg
+
+
+def _draw(seed):
+    rng = np.random.default_rng(5100 + seed)
+    C = int(rng.choice([1, 5, 16, 64, 65, 100, 128]))
+    d = int(rng.integers(0, 13))
+    h, w = int(rng.integers(2, 41)), int(rng.integers(2, 41))
+    return h, w, C, d, int(rng.integers(1, 12)), rng
+
+
+SWEEP = [_draw(seed)[:5] for seed in range(16)]
+_sizes = [n for s in SWEEP for n in s[:2]]
+# the drawn list reaches the paths it is there for: odd sizes, sizes below 12 (cover counts other than 5), 7 and 9 (cover 6),
+# windows larger than the pooled image, more than one pass of four ids, the second channel lane
+assert 7 in _sizes and 9 in _sizes and any(n % 2 for n in _sizes) and any(n < 12 for n in _sizes)
+assert any(2 * s[3] + 1 > max(s[0], s[1]) // 2 for s in SWEEP) and any(s[4] > 4 for s in SWEEP) and any(s[2] > 64 for s in SWEEP)
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_local_tolerance_sweep(ops, seed):
+    h, w, C, d, n_ids, rng = _draw(seed)
+    scale = float(rng.choice([0.05, 0.2]))
+    prev = torch.from_numpy((rng.standard_normal((C, h, w)) * scale).astype(np.float32)).cuda()
+    cur = torch.from_numpy((rng.standard_normal((C, h, w)) * scale).astype(np.float32)).cuda()
+    lab = rng.integers(-1, n_ids, size=(h, w)).astype(np.int32)
+    lab[0, 0] = 0  # (pixel (0, 0) then has a winner for object 0 -- its own window centre -- whatever else was drawn)
+    gout = torch.from_numpy(rng.standard_normal((h, w, n_ids)).astype(np.float32)).cuda()
+    layout = "cmajor" if rng.random() < 0.5 else "rowmajor"
+    tolerance_local(ops, "sweep %d" % seed, prev, cur, torch.from_numpy(lab).cuda(), n_ids, d, gout, layout)
+
+
+def test_local_tolerance_cover_limited_lists(ops):
+    """(h, w) = (7, 9), d = 4, one object, every label 0: a pooled cell's list is limited by cover^2 n_ids = 36, not by 81"""
+    cap = R.max_cover(3, 7) * R.max_cover(4, 9) * 1
+    assert cap == 36 < (2 * 4 + 1) ** 2
+    g = gen(300)
+    prev, cur = (torch.randn(16, 7, 9, generator=g) * 0.2).cuda(), (torch.randn(16, 7, 9, generator=g) * 0.2).cuda()
+    gout = torch.randn(7, 9, 1, generator=g).cuda()
+    arg = tolerance_local(ops, "cover", prev, cur, torch.zeros(7, 9, dtype=torch.int32).cuda(), 1, 4, gout, "cmajor")
+    assert bool((arg >= 0).all())  # (63 winners on 12 pooled cells)
+
+
+def test_local_tolerance_colliding(ops):
+    """tests/test_match_train_gpu.py's collision-heavy generator (the window minimum collides on few cells), for values"""
+    _, prev, cur, _, lab = colliding(52, 60, 3, 31)
+    gout = torch.randn(52, 60, 3, generator=gen(310)).cuda()
+    arg = tolerance_local(ops, "colliding", prev, cur, lab, 3, 12, gout, "cmajor")
+    assert int((arg >= 0).sum()) > 1000
+
+
+def test_local_tolerance_sparse_ids(ops):
+    """40 ids (ten passes of four in the forward), most pixels unlabelled"""
+    g = gen(320)
+    prev, cur = (torch.randn(16, 21, 22, generator=g) * 0.2).cuda(), (torch.randn(16, 21, 22, generator=g) * 0.2).cuda()
+    lab = torch.randint(0, 40, (21, 22), generator=g).int()
+    lab[torch.rand(21, 22, generator=g) < 0.8] = -1
+    gout = torch.randn(21, 22, 40, generator=g).cuda()
+    arg = tolerance_local(ops, "sparse", prev, cur, lab.cuda(), 40, 3, gout, "rowmajor")
+    assert int((arg >= 0).any(0).any(0).sum()) > 20  # winners for many of the ids

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from conftest import load_golden
+from match_grad_ref import global64 as _global64, local64 as _local64
 from test_intvos_module import TinyExtractor
 
 pytestmark = pytest.mark.gpu
@@ -165,63 +166,7 @@ def test_local_fixture_gradients_through_the_ordered_route(ops, name, downsample
 
 # -------------------------------------------------------------------------------- gradients at the training size: float64
 
-def _global64(ref, qry, arg, wgt, gout):
-    """float64 restatement of the global match on the op's recorded selection: out[n, o] = sum_r wgt[r] |q_n - k_arg[r, n, o]|^2
-    (wgt = 1 for k = 1; the top-k weights the op recorded otherwise), differentiated by autograd"""
-    r64 = ref.detach().double().requires_grad_(True)
-    q64 = qry.detach().double().requires_grad_(True)
-    rows, qs = hwc(r64).reshape(-1, r64.shape[0]), hwc(q64).reshape(-1, q64.shape[0])
-    loss = 0
-    for r in range(arg.shape[0]):
-        a = arg[r].long()
-        valid = (a >= 0).double() * wgt[r].double()
-        for o in range(a.shape[1]):
-            dist = ((qs - rows[a[:, o].clamp(min=0)]) ** 2).sum(1)
-            loss = loss + (dist * valid[:, o] * gout[:, o].double()).sum()
-    return torch.autograd.grad(loss, [r64, q64])
-
-
-def _taps64(n_out, n_in):
-    """F.interpolate(bilinear, align_corners=True) source positions and weights: the constants of the op itself (float32
-    scale = (in - 1) / (out - 1), src = scale * dst, i0 = trunc, l1 = src - i0, l0 = 1 - l1), widened to float64"""
-    scale = (torch.tensor(float(n_in - 1), device="cuda") / torch.tensor(float(n_out - 1), device="cuda")) if n_out > 1 else torch.zeros((), device="cuda")
-    src = scale * torch.arange(n_out, dtype=torch.float32, device="cuda")
-    i0 = src.to(torch.int64).clamp(max=n_in - 1)
-    i1 = (i0 + 1).clamp(max=n_in - 1)
-    l1 = src - i0.float()
-    return i0, i1, (1.0 - l1).double(), l1.double()
-
-
-def _local64(prev, cur, arg, gout, d, downsample):
-    """float64 restatement of the local match on the op's recorded winning offsets (IntVOS.py:266-313, :398-432): gathers the
-    selected candidate of every (pixel, object) and does not re-run the min"""
-    p64 = prev.detach().double().requires_grad_(True)
-    c64 = cur.detach().double().requires_grad_(True)
-    h, w = arg.shape[:2]
-    P = 2 * d + 1
-    ys, xs, os_ = torch.nonzero(arg >= 0, as_tuple=True)
-    l = arg[ys, xs, os_].long()
-    g = gout[ys, xs, os_].double()
-    dy, dx = l // P - d, l % P - d
-    if downsample:
-        xp = torch.nn.functional.avg_pool2d(c64[None], 2)[0]
-        yp = torch.nn.functional.avg_pool2d(p64[None], 2)[0]
-        hp, wp = xp.shape[1:]
-        i0, i1, ly0, ly1 = _taps64(h, hp)
-        j0, j1, lx0, lx1 = _taps64(w, wp)
-        val = 0
-        for ti, wy in ((i0[ys], ly0[ys]), (i1[ys], ly1[ys])):
-            for tj, wx in ((j0[xs], lx0[xs]), (j1[xs], lx1[xs])):
-                qi, qj = ti + dy, tj + dx
-                inside = (qi >= 0) & (qi < hp) & (qj >= 0) & (qj < wp)
-                dist = ((xp[:, ti, tj] - yp[:, qi.clamp(0, hp - 1), qj.clamp(0, wp - 1)]) ** 2).sum(0)
-                vn = torch.where(inside, (torch.sigmoid(dist) - 0.5) * 2, torch.ones_like(dist))
-                val = val + wy * wx * vn
-    else:
-        qi, qj = ys + dy, xs + dx
-        assert bool(((qi >= 0) & (qi < h) & (qj >= 0) & (qj < w)).all())  # (an outside neighbour is 1e20 away: it cannot win)
-        val = ((c64[:, ys, xs] - p64[:, qi, qj]) ** 2).sum(0)
-    return torch.autograd.grad((val * g).sum(), [p64, c64])
+# (_global64 / _local64: the float64 restatements on the op's recorded selection, tests/match_grad_ref.py)
 
 
 def _both_routes(fn):
