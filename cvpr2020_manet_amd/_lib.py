@@ -134,6 +134,8 @@ SIGNATURES = {
     "manet_head_train_bytes": (_i, [_i, _i, _i, _i, _i, _i, _szp, _szp]),
     "manet_head_train_forward_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "manet_head_train_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "manet_head_input_forward_f32": (_i, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "manet_head_input_backward_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "manet_loss_ce_topk_workspace_bytes": (_i, [_i, _i, _i, _szp]),
     "manet_loss_ce_pixels_f32": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "manet_loss_ce_topk_forward_f32": (_i, [_vp, _i64, _i64, _i64, _i64, _vp, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i64, _f,

@@ -25,6 +25,10 @@ pointers, so the backward is explicit:
   DynamicSegHeadFn  a whole DynamicSegHead's training step as one node: the existing depthwise, BatchNorm + ReLU and 1x1
                   launchers sequenced in C, the output conv fused with the BatchNorm + ReLU in front of it
                   (csrc/head_train.hip); ops.dynamic_seghead_train, IntVOS(train_kernels="fused").
+  HeadInputFn      the heads' input in training (IntVOS.py:663-671, :741-758: repeat, permutes, the label compare, the cats and
+                  the global map's normalisation) as one node (csrc/head_input_train.hip); ops.head_input_train,
+                  IntVOS(train_inputs="fused").
+  DynamicSegHeadPartsFn  HeadInputFn and DynamicSegHeadFn as one node: maps -> logits; ops.dynamic_seghead_train_parts.
   UpsampledCrossEntropyTopKFn  the loss behind the head (train_stage1.py:126-153, networks/loss.py:44-81): bilinear upsample,
                   cross-entropy, hard-pixel top-k and mean as one op, deterministic forward and backward (csrc/loss_train.hip);
                   ops.upsampled_cross_entropy_topk, networks.loss.Added_CrossEntropyLoss.
@@ -525,6 +529,57 @@ def _ptr_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[_ptr(t) for t in tensors])
 
 
+def _head_train_forward(ctx, head, x, params):
+    """manet_head_train_forward_f32 on a contiguous x -> (logits, the saved activations, the parameters to keep); what the
+    backward needs besides tensors goes onto `ctx`.  DynamicSegHeadFn and DynamicSegHeadPartsFn share it."""
+    tensors = ops.dynamic_seghead_tensors(head)
+    bns = ops.dynamic_seghead_bns(head)
+    B, Cin, h, w = x.shape
+    Cmid, K = head.conv.in_channels, head.layer1.conv1.kernel_size[0]
+    dev = x.device
+    saved_bytes, ws_bytes = _head_bytes(B, Cin, Cmid, h, w, K)
+    saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
+    logits = torch.empty((B, 1, h, w), dtype=torch.float32, device=dev)
+    training = (ctypes.c_int * 8)(*[1 if bn.training else 0 for bn in bns])
+    momentum = (ctypes.c_float * 8)(*[float(bn.momentum) for bn in bns])
+    eps = (ctypes.c_float * 8)(*[float(bn.eps) for bn in bns])
+    with _on(dev):
+        ws = _workspace(dev, "head_train", ws_bytes)
+        _lib.call("manet_head_train_forward_f32", x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(tensors), training, momentum,
+                  eps, saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, logits.data_ptr(), _stream_ptr(dev))
+    # the backward reads parameters, not running statistics: those slots stay NULL there
+    ctx.slots = [i for i, name in enumerate(ops.HEAD_BLOCK_TENSORS * 4 + ("conv.weight", "conv.bias")) if "running" not in name]
+    ctx.present = [p is not None for p in params]
+    ctx.dims = (B, Cin, Cmid, h, w, K)
+    ctx.training = training
+    return logits, saved, [p for p in params if p is not None]
+
+
+def _head_train_backward(ctx, x, saved, kept, grad_out, need_x, need_params):
+    """manet_head_train_backward_f32 -> (grad_x or None, the parameters' gradients in the order of `params`, None where not
+    needed); need_params: the needs_input_grad entries of `params`.  (None, None) when no gradient at all is needed."""
+    B, Cin, Cmid, h, w, K = ctx.dims
+    dev = x.device
+    it = iter(kept)
+    params = [next(it) if present else None for present in ctx.present]
+    need = [present and need_params[j] for j, present in enumerate(ctx.present)]
+    if not (need_x or any(need)):
+        return None, None
+    g = grad_out.contiguous().float()
+    gx = torch.empty_like(x) if need_x else None
+    grads = [torch.empty_like(p) if n else None for p, n in zip(params, need)]
+    p50, g50 = [None] * 50, [None] * 50
+    for slot, p, gp in zip(ctx.slots, params, grads):
+        p50[slot], g50[slot] = p, gp
+    saved_bytes, ws_bytes = _head_bytes(B, Cin, Cmid, h, w, K)
+    with _on(dev):
+        ws = _workspace(dev, "head_train", ws_bytes)
+        _lib.call("manet_head_train_backward_f32", g.data_ptr(), x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(p50),
+                  ctx.training, saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, _ptr_array(g50), _ptr(gx),
+                  _stream_ptr(dev))
+    return gx, grads
+
+
 class DynamicSegHeadFn(torch.autograd.Function):
     """A whole DynamicSegHead (IntVOS.py:509-525: four _split_separable_conv2d blocks and conv = Conv2d(C, 1, 1)) in training as
     one node: apply(head, x, *params), params = the head's 34 parameters in the order of ops.dynamic_seghead_tensors without the
@@ -537,52 +592,103 @@ class DynamicSegHeadFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, head, x, *params):
         x = x.contiguous()
-        tensors = ops.dynamic_seghead_tensors(head)
-        bns = ops.dynamic_seghead_bns(head)
-        B, Cin, h, w = x.shape
-        Cmid, K = head.conv.in_channels, head.layer1.conv1.kernel_size[0]
-        dev = x.device
-        saved_bytes, ws_bytes = _head_bytes(B, Cin, Cmid, h, w, K)
-        saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
-        logits = torch.empty((B, 1, h, w), dtype=torch.float32, device=dev)
-        training = (ctypes.c_int * 8)(*[1 if bn.training else 0 for bn in bns])
-        momentum = (ctypes.c_float * 8)(*[float(bn.momentum) for bn in bns])
-        eps = (ctypes.c_float * 8)(*[float(bn.eps) for bn in bns])
-        with _on(dev):
-            ws = _workspace(dev, "head_train", ws_bytes)
-            _lib.call("manet_head_train_forward_f32", x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(tensors), training, momentum,
-                      eps, saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, logits.data_ptr(), _stream_ptr(dev))
-        # the backward reads parameters, not running statistics: those slots stay NULL there
-        ctx.slots = [i for i, name in enumerate(ops.HEAD_BLOCK_TENSORS * 4 + ("conv.weight", "conv.bias")) if "running" not in name]
-        ctx.present = [p is not None for p in params]
-        ctx.save_for_backward(x, saved, *[p for p in params if p is not None])
-        ctx.dims = (B, Cin, Cmid, h, w, K)
-        ctx.training = training
+        logits, saved, kept = _head_train_forward(ctx, head, x, params)
+        ctx.save_for_backward(x, saved, *kept)
         return logits
 
     @staticmethod
     def backward(ctx, grad_out):
         x, saved, *kept = ctx.saved_tensors
-        B, Cin, Cmid, h, w, K = ctx.dims
-        dev = x.device
-        it = iter(kept)
-        params = [next(it) if present else None for present in ctx.present]
-        need = [present and ctx.needs_input_grad[2 + j] for j, present in enumerate(ctx.present)]
-        if not (ctx.needs_input_grad[1] or any(need)):
-            return (None,) * (2 + len(params))
-        g = grad_out.contiguous().float()
-        gx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
-        grads = [torch.empty_like(p) if n else None for p, n in zip(params, need)]
-        p50, g50 = [None] * 50, [None] * 50
-        for slot, p, gp in zip(ctx.slots, params, grads):
-            p50[slot], g50[slot] = p, gp
-        saved_bytes, ws_bytes = _head_bytes(B, Cin, Cmid, h, w, K)
-        with _on(dev):
-            ws = _workspace(dev, "head_train", ws_bytes)
-            _lib.call("manet_head_train_backward_f32", g.data_ptr(), x.data_ptr(), B, Cin, Cmid, h, w, K, _ptr_array(p50),
-                      ctx.training, saved.data_ptr(), saved_bytes, ws.data_ptr(), ws_bytes, _ptr_array(g50), _ptr(gx),
-                      _stream_ptr(dev))
+        gx, grads = _head_train_backward(ctx, x, saved, kept, grad_out, ctx.needs_input_grad[1], ctx.needs_input_grad[2:])
+        if grads is None:
+            return (None,) * (2 + len(ctx.present))
         return (None, gx) + tuple(grads)
+
+
+def _head_input_forward(ctx, embedding, maps, planes, n_ids, normalize_first):
+    """manet_head_input_forward_f32 -> (x [n_ids, C + maps + planes, h, w], the normalised map 0 or None); the shapes and the
+    embedding's layout the backward needs go onto `ctx`.  maps: float32 tensors of h*w*n_ids elements ([h, w, n_ids] order, any
+    view shape); planes: flat int32 [h*w] (ops._head_input_operands has checked both)."""
+    C, h, w = embedding.shape
+    dev = embedding.device
+    maps = [m.contiguous() for m in maps]
+    x = torch.empty((n_ids, C + len(maps) + len(planes), h, w), dtype=torch.float32, device=dev)
+    norm = torch.empty(h * w * n_ids, dtype=torch.float32, device=dev) if normalize_first else None
+    with _on(dev):
+        _lib.call("manet_head_input_forward_f32", *_strided(embedding), *[_ptr(m) for m in (maps + [None, None])[:2]],
+                  *[_ptr(t) for t in (list(planes) + [None])[:2]], C, h, w, n_ids, len(maps), len(planes),
+                  1 if normalize_first else 0, x.data_ptr(), _ptr(norm), _stream_ptr(dev))
+    ctx.input_dims = (C, h, w, n_ids, len(maps), len(planes), bool(normalize_first))
+    ctx.emb_layout = (embedding.shape, embedding.stride() if _dense(embedding) else None)
+    ctx.map_shapes = [m.shape for m in maps]
+    return x, norm
+
+
+def _head_input_backward(ctx, gx, norm, need_emb, need_maps):
+    """manet_head_input_backward_f32 on a contiguous gx -> (grad_embedding in the embedding's own layout, [grad_map_j]); None
+    where not needed, and no launch when nothing is"""
+    C, h, w, n_ids, n_maps, n_planes, normalize_first = ctx.input_dims
+    dev = gx.device
+    ge = None
+    if need_emb:
+        shape, stride = ctx.emb_layout
+        ge = (torch.empty(shape, dtype=torch.float32, device=dev) if stride is None
+              else torch.empty_strided(shape, stride, dtype=torch.float32, device=dev))
+    gm = [torch.empty(shape, dtype=torch.float32, device=dev) if need else None for shape, need in zip(ctx.map_shapes, need_maps)]
+    if ge is not None or any(m is not None for m in gm):
+        with _on(dev):
+            _lib.call("manet_head_input_backward_f32", gx.data_ptr(), _ptr(norm), C, h, w, n_ids, n_maps, n_planes,
+                      1 if normalize_first else 0, *_optional(ge, 0, 0, 0), *[_ptr(m) for m in (gm + [None, None])[:2]],
+                      _stream_ptr(dev))
+    return ge, (gm + [None, None])[:2]
+
+
+class HeadInputFn(torch.autograd.Function):
+    """The heads' input in training (IntVOS.py:663-671, :741-758) as one node: apply(embedding, map0, map1, planes, n_ids,
+    normalize_first) -> x [n_ids, C + maps + planes, h, w] = cat(embedding repeated per object, the maps permuted to [n_ids, 1, h,
+    w] -- map 0 through (sigmoid(d) - 0.5) * 2 when normalize_first --, labels == object).  map0 / map1: tensors or None;
+    planes: a tuple of flat int32 label planes.  Forward manet_head_input_forward_f32; backward manet_head_input_backward_f32,
+    asked only for the gradients needed (embedding, map0, map1).  It keeps the normalised map 0, never x."""
+
+    @staticmethod
+    def forward(ctx, embedding, map0, map1, planes, n_ids, normalize_first):
+        x, norm = _head_input_forward(ctx, embedding, [m for m in (map0, map1) if m is not None], planes, n_ids, normalize_first)
+        ctx.save_for_backward(*([norm] if norm is not None else []))
+        return x
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        norm = ctx.saved_tensors[0] if ctx.saved_tensors else None
+        ge, gm = _head_input_backward(ctx, grad_x.contiguous().float(), norm, ctx.needs_input_grad[0], ctx.needs_input_grad[1:3])
+        return ge, gm[0], gm[1], None, None, None
+
+
+class DynamicSegHeadPartsFn(torch.autograd.Function):
+    """HeadInputFn and DynamicSegHeadFn as ONE node: apply(head, embedding, map0, map1, planes, n_ids, normalize_first, *params)
+    -> logits [n_ids, 1, h, w].  Forward: the assembly kernel into x, then manet_head_train_forward_f32 exactly as
+    DynamicSegHeadFn calls it; backward: manet_head_train_backward_f32, then the assembly's backward on its grad_x.  With a
+    frozen embedding and no differentiated map (train_stage2.py: the embedding under no_grad, the interaction head has no maps)
+    nobody needs grad_x and layer 1's depthwise backward-data is skipped."""
+
+    @staticmethod
+    def forward(ctx, head, embedding, map0, map1, planes, n_ids, normalize_first, *params):
+        x, norm = _head_input_forward(ctx, embedding, [m for m in (map0, map1) if m is not None], planes, n_ids, normalize_first)
+        logits, saved, kept = _head_train_forward(ctx, head, x, params)
+        ctx.has_norm = norm is not None
+        ctx.save_for_backward(x, saved, *([norm] if norm is not None else []), *kept)
+        return logits
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, saved, *kept = ctx.saved_tensors
+        norm = kept.pop(0) if ctx.has_norm else None
+        need_emb, need_maps = ctx.needs_input_grad[1], ctx.needs_input_grad[2:4]
+        need_maps = [need and j < len(ctx.map_shapes) for j, need in enumerate(need_maps)]
+        gx, grads = _head_train_backward(ctx, x, saved, kept, grad_out, need_emb or any(need_maps), ctx.needs_input_grad[7:])
+        if grads is None:
+            return (None,) * (7 + len(ctx.present))
+        ge, gm = _head_input_backward(ctx, gx, norm, need_emb, need_maps) if gx is not None else (None, [None, None])
+        return (None, ge, gm[0], gm[1], None, None, None) + tuple(grads)
 
 
 class UpsampledCrossEntropyTopKFn(torch.autograd.Function):

@@ -176,6 +176,18 @@ def _train_match_mode(value):
     return value
 
 
+# the heads' input in training (prop_seghead / int_seghead outside the inference fast path): "framework" (the reference's
+# repeat / permute / compare / cat ops and the framework's sigmoid, a dozen launches and autograd nodes) | "fused"
+# (csrc/head_input_train.hip: one launch each way, and ONE node from the maps to the logits where the head runs fused)
+_TRAIN_INPUTS_MODES = ("framework", "fused")
+
+
+def _train_inputs_mode(value):
+    if value not in _TRAIN_INPUTS_MODES:
+        raise ValueError("train_inputs=%r ('framework' or 'fused')" % (value,))
+    return value
+
+
 _VOLUME_DTYPES = {"f32": torch.float32, "f16": torch.float16}
 
 
@@ -573,6 +585,24 @@ def _run_head(head, embedding_chw, per_object, memo=None):
     return head(torch.cat((embedding_chw.unsqueeze(0).repeat((n, 1, 1, 1)), per_object), 1))
 
 
+def _fused_inputs_ok(mode, head, embedding):
+    """train_inputs="fused" applies: the head is outside the inference fast path (training mode or grad enabled) and the
+    embeddings are fp32 on the GPU"""
+    return (mode == "fused" and head is not None and (head.training or torch.is_grad_enabled())
+            and embedding.is_cuda and embedding.dtype == torch.float32)
+
+
+def _run_head_parts(head, embedding_chw, maps, label_planes, n_ids, normalize_first=False):
+    """head(its input assembled from the parts) under train_inputs="fused": ONE autograd node from the maps to the logits
+    (ops.dynamic_seghead_train_parts) where _train_fused_ok holds for the assembled input, else ops.head_input_train -- one node
+    -- followed by the head as it runs on any input ("all", True, the framework's modules, IntSegHead)"""
+    c, h, w = embedding_chw.shape
+    if isinstance(head, DynamicSegHead) and not head.layer1._fast(embedding_chw) and _train_fused_ok(
+            head, embedding_chw.new_empty((0, c + len(maps) + len(label_planes), h, w))):  # (a stand-in with x's channels)
+        return ops.dynamic_seghead_train_parts(head, embedding_chw, maps, label_planes, n_ids, normalize_first)
+    return head(ops.head_input_train(embedding_chw, maps, label_planes, n_ids, normalize_first))
+
+
 # --------------------------------------------------------------------------------------------------
 _ids_cache = {}
 
@@ -605,7 +635,7 @@ class IntVOS(nn.Module):
     """reference IntVOS.py:530-764: same constructor, methods, dict conventions, state-dict keys."""
 
     def __init__(self, cfg, feature_extracter, compute=None, emb_dtype=None, pointwise=None, cache_frames=None,
-                 train_kernels=None, train_match=None, local_volume_dtype=None):
+                 train_kernels=None, train_match=None, local_volume_dtype=None, train_inputs=None):
         """cfg, feature_extracter: as the reference.  The rest is optional and this implementation's only (default: the
         cfg's MODEL_MATCH_COMPUTE / MODEL_EMB_DTYPE / MODEL_HEAD_POINTWISE / MODEL_CACHE_FRAMES when it has them, else
         "f32" / "f32" / "f32" / True):
@@ -628,6 +658,11 @@ class IntVOS(nn.Module):
                         in its last bits from run to run; "ordered" the atomic-free kernels of csrc/match_train.hip: the same bits
                         on every run (with train_kernels="fused" and the fused loss the whole step behind the encoder is
                         reproducible), a sparse local backward and a faster training forward of the local match
+          train_inputs  the heads' input in training: "framework" (default; cfg's MODEL_TRAIN_INPUTS when it has it) the
+                        reference's repeat / permute / compare / cat ops and the framework's sigmoid; "fused" one assembly
+                        launch each way (ops.head_input_train) outside the inference fast path on fp32 GPU embeddings, and
+                        with train_kernels="fused" ONE autograd node from the match maps to the logits
+                        (ops.dynamic_seghead_train_parts): fewer nodes, the same results
           local_volume_dtype  storage type of the stored local-match volumes (prepare_local_volumes, the lazy path, the
                         interaction head's self-match): "f32" (default; cfg's MODEL_LOCAL_VOLUME_DTYPE when it has it) the same
                         bits as the fused kernel | "f16" every normalised window distance rounded once to half: half the bytes,
@@ -694,6 +729,8 @@ class IntVOS(nn.Module):
         use_train_kernels(self, self.train_kernels)
         # (a plain attribute: not a buffer, not in the state dict)
         self.train_match = _train_match_mode(train_match if train_match is not None else getattr(cfg, "MODEL_TRAIN_MATCH", "atomic"))
+        self.train_inputs = _train_inputs_mode(
+            train_inputs if train_inputs is not None else getattr(cfg, "MODEL_TRAIN_INPUTS", "framework"))
 
     @property
     def local_volume_dtype(self):
@@ -1228,6 +1265,10 @@ class IntVOS(nn.Module):
                 torch.is_grad_enabled() and (ref_frame_embedding.requires_grad or current_frame_embedding.requires_grad
                                              or previous_frame_embedding.requires_grad))
             fused_local = use_local_map and inference and self._local_radius() >= 0
+            fused_inputs = _fused_inputs_ok(self.train_inputs, dynamic_seghead, current_frame_embedding)
+            # train_inputs="fused", a differentiated match without a stored map: the raw distances go to the assembly kernel,
+            # which normalises them on the way (with a stored map the normalise + min-merge stay in front of it)
+            norm_first = bool(fused_inputs and not inference and mem is None and normalize_nearest_neighbor_distances)
             pre = None
             if global_map_precomputed is not None and seq_names[n] in global_map_precomputed:
                 pre = global_map_precomputed[seq_names[n]].get(int(frame_num[n]))
@@ -1287,7 +1328,7 @@ class IntVOS(nn.Module):
             else:
                 nn_features_n = ops.global_match(ref_emb, seq_current_frame_embedding, ref_lab() if callable(ref_lab) else ref_lab,
                                                  n_ids, k_nearest_neighbors=k_nearest_neighbors, compute=self.compute,
-                                                 normalize=bool(normalize_nearest_neighbor_distances),
+                                                 normalize=bool(normalize_nearest_neighbor_distances) and not norm_first,
                                                  mem=mem, **_match_route(self.train_match)).view(1, h, w, n_ids, 1)
 
             # ---- local map
@@ -1358,6 +1399,13 @@ class IntVOS(nn.Module):
 
             # ---- head input [n_ids, C+3, h, w] (:663-673)
             pred_ = None
+            if fused_inputs and all(m.is_cuda and m.dtype == torch.float32 and m.numel() == h * w * n_ids
+                                    for m in (nn_features_n, prev_frame_nn_features_n)):
+                # training route of the input (train_inputs="fused"): the maps and the label plane as they are
+                pred_ = _run_head_parts(dynamic_seghead, current_frame_embedding[n], [nn_features_n, prev_frame_nn_features_n],
+                                        [seq_previous_frame_label], n_ids, normalize_first=norm_first)
+            elif norm_first:  # (a local-map table of another type: the framework's ops below, on the normalised map)
+                nn_features_n = (torch.sigmoid(nn_features_n) - 0.5) * 2
             native_maps = (inference and nn_features_n.is_cuda and nn_features_n.dtype == torch.float32
                            and prev_frame_nn_features_n.dtype == torch.float32
                            and nn_features_n.numel() == h * w * n_ids and prev_frame_nn_features_n.numel() == h * w * n_ids)
@@ -1448,6 +1496,14 @@ class IntVOS(nn.Module):
                     mirror[2][(int(frame_num[n]), interaction_num - 1)] = 0.0
                 local_map_dics = (local_map_tmp_dic, local_map_dist_dic)
             # ---- head input (:741-760)
+            if _fused_inputs_ok(self.train_inputs, self.inter_seghead, ref_frame_embedding):
+                # training route of the input (train_inputs="fused"): no maps, the two label planes; on the first interaction
+                # "object 0's channel is 1, the others 0" is an all-zero label plane
+                prev_plane = (torch.zeros_like(seq_ref_scribble_label) if first_inter
+                              else scale_prev_round_label[n].permute(1, 2, 0))
+                pred_ = _run_head_parts(self.inter_seghead, ref_frame_embedding[n], [], [seq_ref_scribble_label, prev_plane], n_ids)
+                dic_tmp[seq_names[n]] = pred_.permute(1, 0, 2, 3)
+                continue
             to_cat_scribble_mask_to_cat = (seq_ref_scribble_label.float() == gt_id.float())
             to_cat_scribble_mask_to_cat = to_cat_scribble_mask_to_cat.unsqueeze(-1).permute(2, 3, 0, 1).float()
             if not first_inter:

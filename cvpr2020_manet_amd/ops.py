@@ -1128,6 +1128,23 @@ def dynamic_seghead_bns(head):
     return [bn for blk in (head.layer1, head.layer2, head.layer3, head.layer4) for bn in (blk.bn1, blk.bn2)]
 
 
+def _head_train_params(head, shape):
+    """what both one-node routes of a DynamicSegHead do in front of their autograd Function: F.batch_norm's batch-size check
+    for an input of `shape` [B, C, h, w], and the 34 parameters in the order of dynamic_seghead_tensors without the running
+    statistics (a missing bias: None)"""
+    if any(bn.training for bn in dynamic_seghead_bns(head)) and shape[0] * shape[2] * shape[3] == 1:  # (_verify_batch_size)
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(torch.Size(shape)))
+    tensors = dynamic_seghead_tensors(head)
+    return [t for t, name in zip(tensors, HEAD_BLOCK_TENSORS * 4 + ("conv.weight", "conv.bias")) if "running" not in name]
+
+
+def _head_train_count(head):
+    """... and behind it: num_batches_tracked of the BatchNorms in training, as nn.BatchNorm2d.forward counts"""
+    counters = [bn.num_batches_tracked for bn in dynamic_seghead_bns(head) if bn.training and bn.num_batches_tracked is not None]
+    if counters:
+        torch._foreach_add_(counters, 1)  # (one launch for the eight, not eight)
+
+
 def dynamic_seghead_train(head, x):
     """head(x) for a DynamicSegHead (IntVOS.py:509-525) in training, as ONE differentiable op on HIP kernels: the four blocks
     and the output conv, forward and backward, sequenced in C (manet_head_train_forward_f32 / _backward_f32;
@@ -1139,16 +1156,56 @@ def dynamic_seghead_train(head, x):
     _need_gpu(x, "x")
     if x.dim() != 4 or x.dtype != torch.float32:
         raise ValueError("x must be a float32 [B, C, h, w] tensor")
-    bns = dynamic_seghead_bns(head)
-    if any(bn.training for bn in bns) and x.shape[0] * x.shape[2] * x.shape[3] == 1:  # (F.batch_norm -> _verify_batch_size)
-        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(x.size()))
     from .autograd import DynamicSegHeadFn
-    tensors = dynamic_seghead_tensors(head)
-    params = [t for t, name in zip(tensors, HEAD_BLOCK_TENSORS * 4 + ("conv.weight", "conv.bias")) if "running" not in name]
-    out = DynamicSegHeadFn.apply(head, x, *params)
-    counters = [bn.num_batches_tracked for bn in bns if bn.training and bn.num_batches_tracked is not None]
-    if counters:
-        torch._foreach_add_(counters, 1)  # (one launch for the eight, not eight)
+    out = DynamicSegHeadFn.apply(head, x, *_head_train_params(head, x.shape))
+    _head_train_count(head)
+    return out
+
+
+def _head_input_operands(embedding, maps, label_planes, n_ids):
+    """the assembly's operands, validated -> (embedding [C, h, w] fp32, [map0, map1] padded with None, tuple of flat int32 planes)"""
+    _need_gpu(embedding, "embedding")
+    if embedding.dim() != 3 or embedding.dtype != torch.float32:
+        raise ValueError("embedding must be a float32 [C, h, w] tensor (a 2-byte embedding is widened by the caller)")
+    C, h, w = embedding.shape
+    maps, label_planes = list(maps), list(label_planes)
+    if len(maps) > 2 or not 1 <= len(label_planes) <= 2:
+        raise ValueError("the head input takes 0..2 maps and 1..2 label planes (got %d and %d)" % (len(maps), len(label_planes)))
+    for j, m in enumerate(maps):
+        _need_gpu(m, "maps[%d]" % j)
+        if m.dtype != torch.float32 or m.numel() != h * w * n_ids or m.device != embedding.device:
+            raise ValueError("maps[%d] must hold h*w*n_ids float32 values as [h, w, n_ids] on the embedding's device" % j)
+    planes = tuple(_labels(t, "label_planes[%d]" % l, h * w) for l, t in enumerate(label_planes))
+    return embedding, (maps + [None, None])[:2], planes
+
+
+def head_input_train(embedding, maps, label_planes, n_ids, normalize_first=False):
+    """The head's input in training (IntVOS.py:663-671, :741-758) in one launch and one autograd node (autograd.HeadInputFn,
+    csrc/head_input_train.hip): x [n_ids, C + len(maps) + len(label_planes), h, w] = cat(embedding.unsqueeze(0).repeat(n_ids, 1,
+    1, 1), each map permuted to [n_ids, 1, h, w], (labels == object).float() per plane).  embedding [C, h, w] fp32, any strides;
+    maps: 0..2 float32 tensors of h*w*n_ids elements laid out [h, w, n_ids] (any view shape, as the match ops return them);
+    label_planes: 1..2 integer tensors of h*w labels (a label outside 0..n_ids-1 marks no object).  normalize_first: maps[0]
+    holds raw distances and goes through (sigmoid(d) - 0.5) * 2 on the way (ops.global_match(normalize=False) in front of it:
+    the inference epilogue's bits).  Differentiable w.r.t. the embedding and the maps; only the gradients that are needed are
+    computed."""
+    emb, (map0, map1), planes = _head_input_operands(embedding, maps, label_planes, n_ids)
+    from .autograd import HeadInputFn
+    return HeadInputFn.apply(emb, map0, map1, planes, int(n_ids), bool(normalize_first))
+
+
+def dynamic_seghead_train_parts(head, embedding, maps, label_planes, n_ids, normalize_first=False):
+    """dynamic_seghead_train(head, head_input_train(embedding, maps, label_planes, n_ids, normalize_first)) as ONE autograd node
+    (autograd.DynamicSegHeadPartsFn): the same kernels in the same order, hence the same bits -- logits [n_ids, 1, h, w], the
+    head's parameter gradients, running statistics and num_batches_tracked, and the gradients of the embedding and the maps.
+    With a frozen embedding and no differentiated map the head's input gradient is not computed at all.  The caller has checked
+    the head's eligibility for the assembled input (IntVOS._train_fused_ok)."""
+    emb, (map0, map1), planes = _head_input_operands(embedding, maps, label_planes, n_ids)
+    C, h, w = emb.shape
+    n_maps = (map0 is not None) + (map1 is not None)
+    params = _head_train_params(head, (int(n_ids), C + n_maps + len(planes), h, w))
+    from .autograd import DynamicSegHeadPartsFn
+    out = DynamicSegHeadPartsFn.apply(head, emb, map0, map1, planes, int(n_ids), bool(normalize_first), *params)
+    _head_train_count(head)
     return out
 
 

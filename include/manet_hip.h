@@ -505,6 +505,28 @@ int manet_head_train_backward_f32(const float *grad_logits, const float *x, int 
                                   float *const *params, const int *training, const void *saved, size_t saved_bytes, void *ws,
                                   size_t ws_bytes, float *const *grads, float *grad_x, manet_stream_t stream);
 
+/* The heads' input in training, assembled and taken apart by one launch each (csrc/head_input_train.hip; IntVOS.py:663-671,
+ * :741-758: cat(embedding.unsqueeze(0).repeat(n_ids, 1, 1, 1), permuted match maps, labels == object) and its backward).
+ * x / grad_x [n_ids][C + n_maps + n_planes][h][w] fp32 contiguous.  embedding [C][h][w] fp32 with element strides (es_c, es_h,
+ * es_w); map0 / map1: n_maps (0..2) float maps of h*w*n_ids elements laid out [h][w][n_ids] like the match outputs; labels0 /
+ * labels1: n_planes (1..2) int32 planes [h*w].  1 <= C <= 128, 1 <= n_ids <= 64, normalize_first needs a map, and
+ * n_ids * channels * h * w must fit in 31 bits: anything else, or a missing pointer, returns MANET_E_INVALID before a launch.
+ * No workspace, no atomics; 16-byte accesses when h*w is a multiple of 4, the planes are contiguous and 16-byte aligned.
+ *   manet_head_input_forward_f32   x[o][c][p] = embedding[c][p] (c < C); x[o][C + j][p] = map_j[p * n_ids + o], map 0 through
+ *       (sigmoid(d) - 0.5) * 2 -- the inference epilogue's function and bits -- when normalize_first, that value also written
+ *       to norm_out [h*w*n_ids] (the backward's only saved input; NULL without normalize_first);
+ *       x[o][C + n_maps + l][p] = labels_l[p] == o ? 1 : 0 (a label outside 0..n_ids-1: zeros).
+ *   manet_head_input_backward_f32  grad_embedding[c][p] = ((grad_x[0][c][p] + grad_x[1][c][p]) + ...) in ascending object
+ *       order, one owner per element, written with the strides (gs_c, gs_h, gs_w); grad_map_j[p * n_ids + o] =
+ *       grad_x[o][C + j][p], times 0.5 (1 - y)(1 + y) with y from norm_out for a normalised map 0 (y == 1, a distance of 1e20:
+ *       exactly 0).  A NULL output is not wanted and costs no work. */
+int manet_head_input_forward_f32(const float *embedding, int64_t es_c, int64_t es_h, int64_t es_w, const float *map0,
+                                 const float *map1, const int32_t *labels0, const int32_t *labels1, int C, int h, int w, int n_ids,
+                                 int n_maps, int n_planes, int normalize_first, float *x, float *norm_out, manet_stream_t stream);
+int manet_head_input_backward_f32(const float *grad_x, const float *norm_out, int C, int h, int w, int n_ids, int n_maps,
+                                  int n_planes, int normalize_first, float *grad_embedding, int64_t gs_c, int64_t gs_h, int64_t gs_w,
+                                  float *grad_map0, float *grad_map1, manet_stream_t stream);
+
 /* The training loss behind the head, fused (csrc/loss_train.hip): train_stage1.py:126-153 + networks/loss.py:44-81, i.e.
  *   F.interpolate(logits, (H, W), 'bilinear', align_corners=True) -> CrossEntropyLoss(ignore_index=255, reduction='none')
  *   -> torch.topk(pixel_losses, k, dim=1) -> mean, and its backward.
