@@ -1,5 +1,5 @@
 // Geometry of the fused local-window kernel (csrc/local_match.hip) and of the padded pooled planes it reads, shared
-// with the per-frame prepare kernel (csrc/global_match.hip: manet_frame_prepare writes those planes and the tile table).
+// with the per-frame prepare kernel (csrc/global_prepare.hip: manet_frame_prepare writes those planes and the tile table).
 #pragma once
 #include "manet_common.h"
 

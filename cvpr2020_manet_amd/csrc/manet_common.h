@@ -49,8 +49,8 @@ void manet_mt_launch_local_min_arg(const float *vol, const int32_t *labels, int 
 
 static inline size_t manet_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Per-frame operands written by manet_frame_prepare (csrc/global_match.hip), read by manet_global_match_prepared_ex
-// (the query operand image, at offset 0: a frame workspace IS a MANET_EMB_PACKED query) and by manet_local_match_frames
+// Per-frame operands written by manet_frame_prepare (csrc/global_prepare.hip), read by manet_global_match_prepared_ex
+// (csrc/global_match.hip: the query operand image, at offset 0: a frame workspace IS a MANET_EMB_PACKED query) and by manet_local_match_frames
 // (csrc/local_match.hip: the 2x2-average-pooled plane with its border of the reference's padding value, and the tile
 // table of the fused kernel).  max_distance < 0: no pooled plane (global match only).
 struct ManetFrameLayout {

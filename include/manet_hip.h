@@ -784,7 +784,7 @@ int manet_profile_begin(int max_launches);
  * key 8 = 1: the LDS-weights fp32 1x1 kernel everywhere (2: the resident-weights kernel with 32-channel stages, 3 / 4: its pixel
  *         ranges in whole tiles / half-tile units whatever the launch size),
  * key 10 = 1: the fp32 kernel keeps the host's split count whatever the bank's real size (see split_of_block in
- *         csrc/global_match.hip),
+ *         csrc/global_match.hip; keys 0, 1 and 10 enter the launch plan, match_plan in csrc/global_match_common.h),
  * key 13 = 0: the depthwise kernel tiles a narrow last column with standard tiles.
  * Keys 2, 3, 5, 6, 7, 9, 11 and 12 selected experiment kernels and launch forms that were removed; their numbers stay retired and
  * are refused (MANET_E_INVALID, the error text names the key).

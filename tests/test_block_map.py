@@ -1,4 +1,5 @@
-"""The block -> (query tile, bank split) maps of the global-match kernels (split_of_block, csrc/global_match.hip): every map
+"""The block -> (query tile, bank split) maps of the global-match kernels (split_of_block, csrc/global_match.hip; which map
+a launch gets is the launch plan's choice: match_plan, csrc/global_match_common.h, pinned by tests/test_match_plan.py): every map
 visits every (tile, split) exactly once, and a minimum does not care in which order its partial results arrive -- so every
 map must give the shipped (automatic) map's bits, for the fp32 and the bf16 kernel, on banks whose split count is and is
 not a multiple of the splits-fastest group."""

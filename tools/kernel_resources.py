@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel register / LDS / occupancy table from hipcc -Rpass-analysis=kernel-resource-usage.
-usage: tools/kernel_resources.py cvpr2020_manet_amd/csrc/global_match.hip [name filter]"""
+usage: tools/kernel_resources.py cvpr2020_manet_amd/csrc/<file>.hip [name filter]   (global_match.hip, global_prepare.hip, ...)"""
 import os
 import re
 import subprocess
