@@ -144,7 +144,7 @@ SIGNATURES = {
                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
-COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X3, COMPUTE_BF16_REFINE = 0, 1, 2, 3
+COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X3, COMPUTE_BF16_REFINE, COMPUTE_F16 = 0, 1, 2, 3, 4
 EMB_F32, EMB_BF16, EMB_PACKED = 0, 1, 2
 EPI_NORMALIZE = 1
 EPI_KEYS_ARMED = 2

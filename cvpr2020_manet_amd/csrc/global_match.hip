@@ -15,7 +15,8 @@
 //   * the operands come packed from csrc/global_prepare.hip: bank rows sorted by object id, so every 64-row bank tile
 //     belongs to one object, in the exact LDS image the MFMA loop wants (Geom, csrc/global_match_common.h); a tile is
 //     staged one tile-step ahead, double buffered, one barrier per tile.
-//   * three arithmetic modes: fp32 MFMA (exact), bf16 MFMA on rounded embeddings, and split-bf16
+//   * arithmetic modes: fp32 MFMA (exact), bf16 MFMA on rounded embeddings, fp16 MFMA on rounded embeddings (the bf16
+//     kernels' body on v_mfma_f32_32x32x16_f16: 11 significand bits instead of 8 at the same cost), and split-bf16
 //     (hi+lo, three MFMAs: fp32-class accuracy); top-k (k_nn 2..8) as a variant of the fp32 kernel.  A fourth, the bf16
 //     filter + exact fp32 re-rank (csrc/global_refine.hip), borrows the wide bf16 kernel and the pipelined fp32 kernel.
 //   * the 64 queries x C operand of a wave lives in registers for the whole kernel.
@@ -604,6 +605,21 @@ __global__ __launch_bounds__(256, 2) void global_match_f32_pipe_kernel(const cha
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 #define MANET_BF(x) __builtin_bit_cast(bf16x8_t, x)
 #define MANET_MFMA(a_, b_, c_) c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(MANET_BF(a_), MANET_BF(b_), c_, 0, 0, 0)
+// The two plain kernels (one MFMA per 16 k) are templates on the ELEMENT of their operand images: bf16 (MANET_COMPUTE_BF16) or
+// fp16 (MANET_COMPUTE_F16, v_mfma_f32_32x32x16_f16: the same operand shape, 8 two-byte elements per lane).  Everything else --
+// tiles, staging, schedule, the minimum -- is one __device__ body per kernel; each element has thin __global__ wrappers of its own
+// (global_match_bf16_wide_kernel / _pipe_kernel, f16_match_wide_kernel / _pipe_kernel).
+struct ElemBF16 {};
+struct ElemF16 {};
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+#define MANET_HF(x) __builtin_bit_cast(f16x8_t, x)
+#define MANET_MFMA_E(a_, b_, c_)                                                                               \
+    {                                                                                                          \
+        if constexpr (std::is_same<E, ElemF16>::value)                                                         \
+            c_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(MANET_HF(a_), MANET_HF(b_), c_, 0, 0, 0);              \
+        else                                                                                                   \
+            c_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(MANET_BF(a_), MANET_BF(b_), c_, 0, 0, 0);             \
+    }
 
 // ---------------------------------------------------------------------------------------------
 // main kernel, split-bf16 operands (MANET_COMPUTE_BF16X3): one workgroup = 512 queries x one bank
@@ -762,9 +778,8 @@ __global__ __launch_bounds__(512, 1) void global_match_bf16x3_kernel(const char 
 //     ever follows a barrier directly; two LDS buffers suffice.
 // (A 3-deep LDS ring with counted vmcnt(N) waits -- the DMA two steps ahead -- was measured slower, 0.529 vs
 // 0.498 ms, and removed: DMA latency is not the stall.)
-template <int KSB>
-__global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *__restrict__ bpack,
+template <int KSB, typename E>
+__device__ __forceinline__ void plain_pipe_body(const char *__restrict__ qpack, const char *__restrict__ bpack,
                                    const int *__restrict__ meta, int n_ids, int nQT, int S, long N_pad,
                                    unsigned *__restrict__ keys, int block_map)
 {
@@ -851,10 +866,10 @@ void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *_
         f32x16 c00 = {0}, c01 = {0}, c10 = {0}, c11 = {0};                                         \
         _Pragma("unroll") for (int k = 0; k < KSB; ++k)                                            \
         {                                                                                          \
-            MANET_MFMA(F0[k], q0[k], c00);                                                         \
-            MANET_MFMA(F1[k], q0[k], c10);                                                         \
-            MANET_MFMA(F0[k], q1[k], c01);                                                         \
-            MANET_MFMA(F1[k], q1[k], c11);                                                         \
+            MANET_MFMA_E(F0[k], q0[k], c00);                                                         \
+            MANET_MFMA_E(F1[k], q0[k], c10);                                                         \
+            MANET_MFMA_E(F0[k], q1[k], c01);                                                         \
+            MANET_MFMA_E(F1[k], q1[k], c11);                                                         \
             MANET_LOADF(k, next_base_);                                                            \
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); /* 4 MFMA  */                       \
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0); /* 2 DS read: the refill, right behind them */ \
@@ -900,6 +915,22 @@ void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *_
 #undef MANET_LOADF
     flush(o);
 }
+template <int KSB>
+__global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *__restrict__ bpack,
+                                   const int *__restrict__ meta, int n_ids, int nQT, int S, long N_pad,
+                                   unsigned *__restrict__ keys, int block_map)
+{
+    plain_pipe_body<KSB, ElemBF16>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, block_map);
+}
+// MANET_COMPUTE_F16, C > 106.  (The fp16 kernels are named f16_*: the library's global_match_* kernels are the set they were.)
+template <int KSB>
+__global__ __launch_bounds__(512, 1) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void f16_match_pipe_kernel(const char *__restrict__ qpack, const char *__restrict__ bpack, const int *__restrict__ meta, int n_ids,
+                           int nQT, int S, long N_pad, unsigned *__restrict__ keys, int block_map)
+{
+    plain_pipe_body<KSB, ElemF16>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, block_map);
+}
 
 // ---------------------------------------------------------------------------------------------
 // "Wide" form of the pipelined plain-bf16 kernel: 4 waves per workgroup, each wave owns 128 queries (four
@@ -916,8 +947,8 @@ void global_match_bf16_pipe_kernel(const char *__restrict__ qpack, const char *_
 // fill count; an entry that does not fit raises stats[1]).  A pass's 16 distances per lane are first reduced to their minimum --
 // the same eight v_minimum3 the plain kernel spends -- and only a wave in which some lane's minimum passes its threshold
 // takes the slow path that looks at the individual rows.
-template <int KSB, bool FILTER = false>
-__global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const char *__restrict__ qpack,
+template <int KSB, bool FILTER, typename E>
+__device__ __forceinline__ void plain_wide_body(const char *__restrict__ qpack,
                                                                         const char *__restrict__ bpack,
                                                                         const int *__restrict__ meta, int n_ids,
                                                                         int nQT, int S, long N_pad,
@@ -1148,10 +1179,10 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
         f32x16 c0 = {0}, c1 = {0}, c2 = {0}, c3 = {0};                                             \
         _Pragma("unroll") for (int k = 0; k < KSB; ++k)                                            \
         {                                                                                          \
-            MANET_MFMA(F[k], q[0][k], c0);                                                         \
-            MANET_MFMA(F[k], q[1][k], c1);                                                         \
-            MANET_MFMA(F[k], q[2][k], c2);                                                         \
-            MANET_MFMA(F[k], q[3][k], c3);                                                         \
+            MANET_MFMA_E(F[k], q[0][k], c0);                                                         \
+            MANET_MFMA_E(F[k], q[1][k], c1);                                                         \
+            MANET_MFMA_E(F[k], q[2][k], c2);                                                         \
+            MANET_MFMA_E(F[k], q[3][k], c3);                                                         \
             MANET_LOADF(k, next_base_);                                                            \
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0); /* 4 MFMA */                        \
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); /* the refill right behind them */  \
@@ -1194,8 +1225,8 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
         f32x16 c0 = {0}, c1 = {0};                                                                 \
         _Pragma("unroll") for (int k = 0; k < KSB; ++k)                                            \
         {                                                                                          \
-            MANET_MFMA(F[k], q[0][k], c0);                                                         \
-            MANET_MFMA(F[k], q[1][k], c1);                                                         \
+            MANET_MFMA_E(F[k], q[0][k], c0);                                                         \
+            MANET_MFMA_E(F[k], q[1][k], c1);                                                         \
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); /* 2 MFMA */                        \
             __builtin_amdgcn_sched_group_barrier(0x002, 4, 0); /* a slice of the pending test */   \
         }                                                                                          \
@@ -1204,8 +1235,8 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
         pc3 = (f32x16){0};                                                                         \
         _Pragma("unroll") for (int k = 0; k < KSB; ++k)                                            \
         {                                                                                          \
-            MANET_MFMA(F[k], q[2][k], pc2);                                                        \
-            MANET_MFMA(F[k], q[3][k], pc3);                                                        \
+            MANET_MFMA_E(F[k], q[2][k], pc2);                                                        \
+            MANET_MFMA_E(F[k], q[3][k], pc3);                                                        \
             MANET_LOADF(k, next_base_);                                                            \
             __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);                                     \
             __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); /* the refill right behind them */  \
@@ -1320,8 +1351,34 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
         if (lane == 0 && wl_total) atomicAdd(&stats[0], (unsigned long long)wl_total);  // (statistics only)
     }
 }
+template <int KSB, bool FILTER = false>
+__global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const char *__restrict__ qpack,
+                                                                        const char *__restrict__ bpack,
+                                                                        const int *__restrict__ meta, int n_ids,
+                                                                        int nQT, int S, long N_pad,
+                                                                        unsigned *__restrict__ keys, int block_map,
+                                                                        unsigned *__restrict__ thr,
+                                                                        const float *__restrict__ slack,
+                                                                        unsigned long long *__restrict__ stats,
+                                                                        uint2 *__restrict__ list, long bucket_cap,
+                                                                        unsigned *__restrict__ bcnt)
+{
+    plain_wide_body<KSB, FILTER, ElemBF16>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, block_map, thr, slack, stats, list,
+                                           bucket_cap, bcnt);
+}
+// MANET_COMPUTE_F16, C <= 106: the plain form only (the filter form is MANET_COMPUTE_BF16_REFINE's, bf16)
+template <int KSB>
+__global__ __launch_bounds__(256, 2) void f16_match_wide_kernel(const char *__restrict__ qpack, const char *__restrict__ bpack,
+                                                                const int *__restrict__ meta, int n_ids, int nQT, int S, long N_pad,
+                                                                unsigned *__restrict__ keys, int block_map)
+{
+    plain_wide_body<KSB, false, ElemF16>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, block_map, nullptr, nullptr, nullptr, nullptr,
+                                         0L, nullptr);
+}
 
 #undef MANET_MFMA
+#undef MANET_MFMA_E
+#undef MANET_HF
 #undef MANET_BF
 
 
@@ -1467,7 +1524,8 @@ __global__ void zero_strided_kernel(float *__restrict__ p, long n0, long n1, lon
 // splits, block_map word, LDS bytes) is the plan's.  Bracketed for manet_profile_begin / _end (channel 0; the pre-pass: 3; the
 // rescue: by its caller).  The LDS attribute is set per call (cheap, host side): it is per device and the library keeps no state.
 //   plain bf16 -> global_match_bf16_wide_kernel (k-steps 2 / 7), global_match_bf16_pipe_kernel for C > 106 (k-step 9: its
-//   144 operand VGPRs do not fit the wide form; MANET_COMPUTE_BF16_REFINE supports C <= 106); split-bf16 -> the x3 kernel
+//   144 operand VGPRs do not fit the wide form; MANET_COMPUTE_BF16_REFINE supports C <= 106); split-bf16 -> the x3 kernel;
+//   MANET_COMPUTE_F16 -> the fp16 wrappers of the same two bodies, f16_match_wide_kernel<2 / 7> and f16_match_pipe_kernel<9>
 void launch_match(const MatchPlan &P, const MatchArgs &A, hipStream_t st)
 {
     const bool rescue = P.form == MATCH_FORM_REFINE_RESCUE || P.form == MATCH_FORM_REFINE_RESCUE_EXACT;
@@ -1492,6 +1550,10 @@ void launch_match(const MatchPlan &P, const MatchArgs &A, hipStream_t st)
         with_ksb(P.steps, [&](auto k) {
             constexpr int K = decltype(k)::value;
             if (P.compute == MANET_COMPUTE_BF16X3) go(global_match_bf16x3_kernel<K>, 512, A.keys, P.block_map);
+            else if (P.compute == MANET_COMPUTE_F16) {  // (k-step 9 -- C > 106 -- takes the narrow form, as plain bf16)
+                if constexpr (K == 9) go(f16_match_pipe_kernel<K>, 512, A.keys, P.block_map);
+                else go(f16_match_wide_kernel<K>, 256, A.keys, P.block_map);
+            }
             else if constexpr (K == 9) go(global_match_bf16_pipe_kernel<K>, 512, A.keys, P.block_map);
             else if (P.form == MATCH_FORM_REFINE_FILTER)
                 go(global_match_bf16_wide_kernel<K, true>, 256, A.keys, P.block_map, A.thr, A.slack, A.stats, A.list, A.bucket_cap, A.bcnt);

@@ -65,6 +65,16 @@ constexpr int FILTER_TAIL_CUTS = 4;  // pieces each XCD's last split of the filt
 //   query k = C+0..2 : 1, 1, 1                                      bank k = C+0..2 : |k|^2 as hi+mid+lo
 //   query k = C+3..5 : |q|^2 as hi+mid+lo (three bf16 = 24 bits)    bank k = C+3..5 : 1, 1, 1
 // (three bf16 pieces carry an fp32 value exactly; the products with 1 are exact, the sum is fp32.)
+//
+// f16 images (MANET_COMPUTE_F16, v_mfma_f32_32x32x16_f16): the bf16 image's layout with fp16 elements -- -2*f16(q) / f16(k) --
+// and the same six norm slots.  fp16 has a narrow exponent range, so the norm's three pieces are SCALED by powers of two and
+// meet the inverse power on the other side (products of a power of two: exact):
+//   side that carries its norm: p0, p1 * 2^11, p2 * 2^14        other side: 1, 2^-11, 2^-14
+// Every stored piece is zero or a NORMAL fp16 number (split3_f16), whether or not the matrix pipe honours subnormal operands:
+// p0 + p1 + p2 == norm exactly for norms >= 2^-5, within 2^-28 below (asked for: exact from 2^-6, within 2^-25 below -- but the
+// last bit of a norm in [2^-6, 2^-5), 2^-29, times the largest scale whose partner 2^-14 is still normal is subnormal: dropped).
+// A row outside fp16's domain (|row|^2 of the rounded values > 65504, an infinity, a NaN) carries NaN in its first norm slot: all of its distances are NaN.  A bank tile's padding rows carry
+// +inf there (fp16 has no 1e20): their distances are +inf and never win a minimum.
 constexpr int BF16_SPECIAL = 6;  // spare k slots needed behind the C channels
 __host__ __device__ constexpr size_t bank_tile_bytes_u(int units, bool norms)
 {
@@ -179,7 +189,7 @@ Geom geom_of(int C, int compute)
 {
     Geom G;
     if (compute == MANET_COMPUTE_BF16_REFINE) compute = MANET_COMPUTE_BF16;  // same operand images as plain bf16
-    G.compute = compute;
+    G.compute = compute;  // (MANET_COMPUTE_F16 stays: the bf16 image's geometry, fp16 elements)
     if (compute == MANET_COMPUTE_F32) {
         G.steps = pick_ks(C);
         int NG = (G.steps + 3) / 4;
@@ -307,8 +317,8 @@ int check_common(int64_t N, int64_t M0, int C, int n_ids, int k_nn, int compute)
     if (k_nn > 1 && compute != MANET_COMPUTE_F32)
         return manet_set_error(MANET_E_INVALID, "k_nn > 1 needs MANET_COMPUTE_F32");
     if (compute != MANET_COMPUTE_F32 && compute != MANET_COMPUTE_BF16 && compute != MANET_COMPUTE_BF16X3 &&
-        compute != MANET_COMPUTE_BF16_REFINE)
-        return manet_set_error(MANET_E_INVALID, "compute=%d (MANET_COMPUTE_F32 / _BF16 / _BF16X3 / _BF16_REFINE)", compute);
+        compute != MANET_COMPUTE_BF16_REFINE && compute != MANET_COMPUTE_F16)
+        return manet_set_error(MANET_E_INVALID, "compute=%d (MANET_COMPUTE_F32 / _BF16 / _BF16X3 / _BF16_REFINE / _F16)", compute);
     if (compute == MANET_COMPUTE_BF16_REFINE && C + BF16_SPECIAL > 112)
         return manet_set_error(MANET_E_INVALID, "MANET_COMPUTE_BF16_REFINE supports C <= 106 (the wide bf16 kernel)");
     return MANET_OK;
@@ -362,11 +372,12 @@ MatchPlan match_plan(int64_t N, int64_t M0, int C, int n_ids, int k_nn, int comp
     P.T_max = form == MATCH_FORM_REFINE_PRE ? BL.T_sub_max : BL.T_max;
     // resident workgroup slots: f32 and plain bf16 (wide kernel) = 2 x 256-thread workgroups per CU,
     // split-bf16 and the narrow plain-bf16 kernel (C > 106) = 1 x 512-thread workgroup per CU
-    const bool one_per_cu = compute == MANET_COMPUTE_BF16X3 || (compute == MANET_COMPUTE_BF16 && ML.G.steps == 9);
+    const bool plain2 = compute == MANET_COMPUTE_BF16 || compute == MANET_COMPUTE_F16;  // one MFMA per 16 k on 2-byte elements
+    const bool one_per_cu = compute == MANET_COMPUTE_BF16X3 || (plain2 && ML.G.steps == 9);
     P.slots = main && one_per_cu ? 256 : 512;
     // two tile buffers (plain bf16: two tiles per step); the filter adds its candidate sub-lists and the published keys
     const size_t tile_bytes = rescue ? BL.G32.tile_bytes : BL.tile_bytes;
-    P.lds = (size_t)(BL.G.compute == MANET_COMPUTE_BF16 && !rescue ? 4 : 2) * tile_bytes;
+    P.lds = (size_t)((BL.G.compute == MANET_COMPUTE_BF16 || BL.G.compute == MANET_COMPUTE_F16) && !rescue ? 4 : 2) * tile_bytes;
     if (filter) P.lds += (size_t)REFINE_LDS_LIST * 8 + 4 * 256 * 4;
     P.S = pick_splits(P.nQT, P.T_max, P.slots);
     if (main && tune.splits > 0) P.S = (tune.splits + 7) / 8 * 8;  // tuning only
@@ -421,6 +432,33 @@ __device__ __forceinline__ void split3_bf16(float x, unsigned (&p)[3])
     p[1] = f2bf(r);
     r = r - bf2f(p[1]);
     p[2] = f2bf(r);
+}
+
+// fp32 -> fp16, round to nearest even (v_cvt_f16_f32: beyond 65504 -> infinity, NaN stays NaN), and back (exact)
+__device__ __forceinline__ unsigned f2h(float x) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)x); }
+__device__ __forceinline__ float h2f(unsigned b) { return (float)__builtin_bit_cast(_Float16, (unsigned short)b); }
+// ... with a subnormal result replaced by zero: what the norm slots store (see the f16 image)
+__device__ __forceinline__ unsigned f2h_normal(float x)
+{
+    const unsigned b = f2h(x);
+    return (b & 0x7c00u) ? b : 0u;
+}
+
+// a row's squared norm as three SCALED fp16 pieces, p[0] + p[1] * 2^-11 + p[2] * 2^-14 (see the f16 image): each piece zero or
+// normal; the sum equals x for x >= 2^-5 and is within 2^-28 of it below.  x = +inf (a padding row) -> {+inf, 0, 0}; any other
+// value outside [0, 65504], NaN included -> {NaN, 0, 0}.
+__device__ __forceinline__ void split3_f16(float x, unsigned (&p)[3])
+{
+    if (!(x >= 0.0f && x <= 65504.0f)) {
+        p[0] = (x == INFINITY) ? 0x7c00u : 0x7e00u;
+        p[1] = p[2] = 0u;
+        return;
+    }
+    p[0] = f2h_normal(x);
+    float r = x - h2f(p[0]);                    // exact: |r| <= half an ulp of p[0] (or x itself, below 2^-14)
+    p[1] = f2h_normal(r * 2048.0f);
+    r = r - h2f(p[1]) * (1.0f / 2048.0f);       // exact
+    p[2] = f2h_normal(r * 16384.0f);
 }
 
 // embedding element types the pack kernels read (the producer's storage):

@@ -148,6 +148,36 @@ __device__ __forceinline__ uint4 image_unit_bf16(const float *row, int u, int hi
     return make_uint4(e8[0] | (e8[1] << 16), e8[2] | (e8[3] << 16), e8[4] | (e8[5] << 16), e8[6] | (e8[7] << 16));
 }
 
+// MANET_COMPUTE_F16: the same unit with fp16 elements (rounded to nearest even from the staged fp32 value) and the scaled norm
+// pieces against 1, 2^-11, 2^-14 (see Geom)
+template <bool IS_QUERY>
+__device__ __forceinline__ uint4 image_unit_f16(const float *row, int u, int C, float norm)
+{
+    const float scale = IS_QUERY ? -2.0f : 1.0f;  // the query operand is -2q (exact in fp16 up to its overflow: the norm slot's NaN)
+    const int k0 = 16 * (u >> 1) + 8 * (u & 1);
+    unsigned e8[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) e8[e] = f2h(scale * h2f(f2h(row[k0 + e])));
+    if (k0 + 8 > C && k0 < C + BF16_SPECIAL) {  // this unit holds norm slots
+        unsigned piece[3];
+        split3_f16(norm, piece);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int j = k0 + e - C;  // 0..2: bank norm / query constants, 3..5: bank constants / query norm
+            if (j >= 0 && j < BF16_SPECIAL) {
+                const bool norm_slot = IS_QUERY ? (j >= 3) : (j < 3);
+                const int j3 = j % 3;  // (select chains: see image_unit_bf16)
+                const unsigned pj = j3 == 0 ? piece[0] : (j3 == 1 ? piece[1] : piece[2]);
+                const unsigned cj = j3 == 0 ? 0x3c00u : (j3 == 1 ? 0x1000u : 0x0400u);  // 1, 2^-11, 2^-14
+                e8[e] = norm_slot ? pj : cj;
+            }
+        }
+    }
+    return make_uint4(e8[0] | (e8[1] << 16), e8[2] | (e8[3] << 16), e8[4] | (e8[5] << 16), e8[6] | (e8[7] << 16));
+}
+// |row|^2 of a MANET_COMPUTE_F16 row as its norm slot takes it: outside fp16's domain (or NaN) -> NaN
+__device__ __forceinline__ float norm_f16_domain(float n) { return n <= 65504.0f ? n : __builtin_nanf(""); }
+
 // bank (ROWS = 64) and query (ROWS = 32) pack: rows -> MFMA operand image (see Geom).
 // Rows are staged through LDS so that both the global reads (along k for row-major sources, along
 // rows for C-major sources) and the 16-byte image writes are coalesced.  |row|^2 is the k-ascending
@@ -157,8 +187,9 @@ __device__ __forceinline__ uint4 image_unit_bf16(const float *row, int u, int hi
 // ROWS = rows staged per workgroup (a whole number of image blocks); IMG = rows per image block (64: bank tile,
 // 32: query block).  keys != nullptr (query):
 // the rows' match keys are reset to "no candidate" here, which saves the fill launch of the per-frame sequence.
-template <int ROWS, int IMG, typename SRC>
-__global__ __launch_bounds__(256) void pack_rows_kernel(const SRC *__restrict__ src, long s_row,
+// F16 (MANET_COMPUTE_F16) is a compile-time form of this body with kernels of its own (pack_rows_f16_kernel).
+template <int ROWS, int IMG, typename SRC, bool F16>
+__device__ __forceinline__ void pack_rows_body(const SRC *__restrict__ src, long s_row,
                                                         long s_c, const int *__restrict__ src_of,
                                                         const int *__restrict__ meta, long n_rows,
                                                         int C, int compute, int units, int kpad,
@@ -201,11 +232,17 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const SRC *__restrict__ 
     }
     __syncthreads();
     if (tid < ROWS) {
-        float n = pad_norm;
+        float n = F16 && pad_norm > 65504.0f ? INFINITY : pad_norm;  // (fp16 has no 1e20: a bank tile's padding rows carry +inf)
         if (s_src[tid] >= 0) {
             n = 0.0f;
             const float *row = rows + tid * KP;
-            if (compute == MANET_COMPUTE_BF16) {
+            if constexpr (F16) {
+                for (int k = 0; k < C; ++k) {
+                    float x = h2f(f2h(row[k]));
+                    n = fmaf(x, x, n);
+                }
+                n = norm_f16_domain(n);
+            } else if (compute == MANET_COMPUTE_BF16) {
                 for (int k = 0; k < C; ++k) {
                     float x = bf2f(f2bf(row[k]));
                     n = fmaf(x, x, n);
@@ -219,7 +256,13 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const SRC *__restrict__ 
     __syncthreads();
     // image block of staged row r: block (tile * ROWS/IMG + r / IMG), row r % IMG inside it
     char *out0 = dst + tile * (ROWS / IMG) * tile_bytes;
-    if (compute == MANET_COMPUTE_F32) {
+    if constexpr (F16) {
+        for (int item = tid; item < units * ROWS; item += 256) {
+            int r = item % ROWS, u = item / ROWS;
+            *(uint4 *)(out0 + (r / IMG) * tile_bytes + ((long)u * IMG + r % IMG) * 16) =
+                image_unit_f16<IS_QUERY>(rows + r * KP, u, C, s_norm[r]);
+        }
+    } else if (compute == MANET_COMPUTE_F32) {
         for (int item = tid; item < units * ROWS; item += 256) {
             int r = item % ROWS, u = item / ROWS;
             *(f32x4 *)(out0 + (r / IMG) * tile_bytes + ((long)u * IMG + r % IMG) * 16) = image_unit_f32(rows + r * KP, u);
@@ -234,6 +277,23 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const SRC *__restrict__ 
         }
     }
 }
+#define MANET_PACK_ROWS_PARAMS                                                                                          \
+    const SRC *__restrict__ src, long s_row, long s_c, const int *__restrict__ src_of, const int *__restrict__ meta,   \
+        long n_rows, int C, int compute, int units, int kpad, char *__restrict__ dst, long tile_bytes, float pad_norm, \
+        unsigned *__restrict__ keys, long N_pad, int n_ids
+#define MANET_PACK_ROWS_ARGS src, s_row, s_c, src_of, meta, n_rows, C, compute, units, kpad, dst, tile_bytes, pad_norm, keys, N_pad, n_ids
+template <int ROWS, int IMG, typename SRC>
+__global__ __launch_bounds__(256) void pack_rows_kernel(MANET_PACK_ROWS_PARAMS)
+{
+    pack_rows_body<ROWS, IMG, SRC, false>(MANET_PACK_ROWS_ARGS);
+}
+template <int ROWS, int IMG, typename SRC>
+__global__ __launch_bounds__(256) void pack_rows_f16_kernel(MANET_PACK_ROWS_PARAMS)
+{
+    pack_rows_body<ROWS, IMG, SRC, true>(MANET_PACK_ROWS_ARGS);
+}
+#undef MANET_PACK_ROWS_PARAMS
+#undef MANET_PACK_ROWS_ARGS
 
 // ---------------------------------------------------------------------------------------------
 // Per-frame prepare (the producer side of the path): ONE read of a frame's C-major embedding
@@ -267,7 +327,7 @@ struct FramePrep {
     void *emb_out;
     int emb_out_bf16, relu;
     int vec2;   // s_x == 1, even w / strides, aligned base: two pixels per load
-    int rcopy;  // fp32 source + MANET_COMPUTE_BF16: LDS also holds a bf16-rounded copy
+    int rcopy;  // fp32 source + MANET_COMPUTE_BF16 / _F16: LDS also holds a copy rounded to the operand's element type
     int abl;    // always 0 (kept: the hot kernel's argument block stays as measured)
 };
 // VEC2 (r6): the two staging forms are separate instantiations -- as a run-time branch (r3-r5) both lived in every kernel and the
@@ -276,6 +336,7 @@ constexpr int XC = 32;  // full-resolution columns per workgroup
 template <typename SRC, bool VEC2>
 __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
 {
+    const bool F16 = A.compute == MANET_COMPUTE_F16;  // (block-uniform) the fp16 image: fp16 elements, scaled norm pieces
     constexpr int PIX = 2 * XC;
     extern __shared__ __attribute__((aligned(16))) char pack_smem[];
     const int tid = threadIdx.x;
@@ -333,13 +394,18 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
     // rq = the values the bf16 image and its |q|^2 are made from: bf16-rounded.  2-byte sources ARE rounded already (rq = rows);
     // fp32 sources with plain-bf16 arithmetic get a second, rounded copy (A.rcopy) so that neither the norm chain nor the image
     // assembly rounds per use (r3: 5 us of norm chain and 7 us of image assembly in a 20 us launch).
+    // The fp16 image (F16) likewise, rounded to fp16: there only the rounded copy counts as exact.
     const int KP = kpad + 1;
     float *rows = (float *)pack_smem;           // [PIX][KP]
     float *rq = A.rcopy ? rows + (long)PIX * KP : rows;
     const int rp = blockIdx.x / A.nxc, cx = blockIdx.x - rp * A.nxc;
     const int x0 = cx * XC, y0 = 2 * rp;
     // rq holds bf16-exact values (a 2-byte source, the rounded copy, or the embedding epilogue's 2-byte output)
-    const bool bf16_exact = (A.compute == MANET_COMPUTE_BF16) && (A.rcopy || sizeof(SRC) == 2 || (A.scale && A.emb_out_bf16));
+    // (MANET_COMPUTE_F16: the rounded copy only -- a bf16 value need not be an fp16 value)
+    const bool plain2 = F16 || A.compute == MANET_COMPUTE_BF16;  // one 2-byte image made from rounded values
+    const bool bf16_exact = F16 ? (bool)A.rcopy
+                                : (A.compute == MANET_COMPUTE_BF16) && (A.rcopy || sizeof(SRC) == 2 || (A.scale && A.emb_out_bf16));
+    auto round2 = [F16](float x) { return F16 ? h2f(f2h(x)) : bf2f(f2bf(x)); };
     // The launch is LATENCY-bound, not bandwidth-bound (1.6 workgroups per CU, 27 MB per frame; ablations in DESIGN 3.3): every
     // load of the workgroup is issued before the first one is waited for -- one memory round trip per workgroup.
     if constexpr (VEC2) {  // two horizontally adjacent pixels per lane (8-byte / 4-byte loads): half the load instructions
@@ -390,7 +456,7 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
                     if (k < C) {
                         const float a = in ? va[j] : 0.0f, b = in ? vb[j] : 0.0f;
                         r0[k] = a; r0[KP + k] = b;
-                        if (A.rcopy) { q0[k] = bf2f(f2bf(a)); q0[KP + k] = bf2f(f2bf(b)); }
+                        if (A.rcopy) { q0[k] = round2(a); q0[KP + k] = round2(b); }
                     }
                 }
             }
@@ -437,7 +503,7 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
                     if (k < C) {
                         const float a = in ? v[j] : 0.0f;
                         rp_[k] = a;
-                        if (A.rcopy) qp_[k] = bf2f(f2bf(a));
+                        if (A.rcopy) qp_[k] = round2(a);
                     }
                 }
             }
@@ -466,7 +532,7 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
         const int k0 = 16 * (u >> 1) + 8 * (u & 1);
         unsigned e8[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) e8[e] = __float_as_uint(-2.0f * row[k0 + e]) >> 16;
+        for (int e = 0; e < 8; ++e) e8[e] = F16 ? f2h(-2.0f * row[k0 + e]) : __float_as_uint(-2.0f * row[k0 + e]) >> 16;
         return make_uint4(e8[0] | (e8[1] << 16), e8[2] | (e8[3] << 16), e8[4] | (e8[5] << 16), e8[6] | (e8[7] << 16));
     };
     // (f32 image: the last units / 6 units of every pixel are wave 0's as well -- its share of the store work behind the chain)
@@ -478,8 +544,8 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
         const long n = (long)y * A.w + x;
         float nrm = 0.0f;
         {  // |q|^2: the k-ascending fmaf chain of the oracle, as pack_rows_kernel (reads batched ahead)
-            const float *row = (A.compute == MANET_COMPUTE_BF16 ? rq : rows) + p * KP;
-            const bool rnd = (A.compute == MANET_COMPUTE_BF16) && !bf16_exact;
+            const float *row = (plain2 ? rq : rows) + p * KP;
+            const bool rnd = plain2 && !bf16_exact;
             int k = 0;
             for (; k + 10 <= C; k += 10) {
                 float v[10];
@@ -487,14 +553,15 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
                 for (int j = 0; j < 10; ++j) v[j] = row[k + j];
 #pragma unroll
                 for (int j = 0; j < 10; ++j) {
-                    const float xv = rnd ? bf2f(f2bf(v[j])) : v[j];
+                    const float xv = rnd ? round2(v[j]) : v[j];
                     nrm = fmaf(xv, xv, nrm);
                 }
             }
             for (; k < C; ++k) {
-                const float xv = rnd ? bf2f(f2bf(row[k])) : row[k];
+                const float xv = rnd ? round2(row[k]) : row[k];
                 nrm = fmaf(xv, xv, nrm);
             }
+            if (F16) nrm = norm_f16_domain(nrm);
         }
         if (in) {
             if (f32img) {
@@ -502,7 +569,10 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
                 for (int u = u_split; u < units; ++u) *(f32x4 *)image_addr(n, u) = image_unit_f32(rows + p * KP, u);
             } else {
                 for (int u = 0; u < units; ++u)
-                    if (unit_is_special(u)) *(uint4 *)image_addr(n, u) = image_unit_bf16<true>(rows + p * KP, u, hi_units, C, nrm);
+                    if (unit_is_special(u)) {
+                        if (F16) *(uint4 *)image_addr(n, u) = image_unit_f16<true>(rows + p * KP, u, C, nrm);
+                        else *(uint4 *)image_addr(n, u) = image_unit_bf16<true>(rows + p * KP, u, hi_units, C, nrm);
+                    }
             }
         }
     }
@@ -528,6 +598,7 @@ __global__ __launch_bounds__(256) void frame_prepare_kernel(const FramePrep A)
             if (f32img) *(f32x4 *)image_addr(n, u) = image_unit_f32(rows + p * KP, u);
             else if (unit_is_special(u)) continue;  // (wave 0, behind the norm chain)
             else if (bf16_exact) *(uint4 *)image_addr(n, u) = unit_bf16_exact(rq + p * KP, u);
+            else if (F16) *(uint4 *)image_addr(n, u) = image_unit_f16<true>(rows + p * KP, u, C, 0.0f);
             else *(uint4 *)image_addr(n, u) = image_unit_bf16<true>(rows + p * KP, u, hi_units, C, 0.0f);
         }
     }
@@ -621,6 +692,19 @@ int launch_bank_pack(const void *src, int emb_dtype, long s_row, long s_c, const
 {
     if (ntiles <= 0) return MANET_OK;
     const size_t lds = (size_t)BT * (G.kpad + 1) * sizeof(float) + 2 * BT * sizeof(int);
+    if (emb_dtype != MANET_EMB_F32 && emb_dtype != MANET_EMB_BF16)
+        return manet_set_error(MANET_E_INVALID, "embedding dtype %d (MANET_EMB_F32 / MANET_EMB_BF16)", emb_dtype);
+    if (G.compute == MANET_COMPUTE_F16) {
+        if (emb_dtype == MANET_EMB_F32)
+            hipLaunchKernelGGL((pack_rows_f16_kernel<BT, BT, float>), dim3((unsigned)ntiles), dim3(256), lds, st, (const float *)src,
+                               s_row, s_c, src_of, meta, n_rows, C, G.compute, G.units, G.kpad, dst, (long)G.tile_bytes,
+                               MANET_WRONG_LABEL_PADDING_DISTANCE, (unsigned *)nullptr, 0L, 0);
+        else
+            hipLaunchKernelGGL((pack_rows_f16_kernel<BT, BT, unsigned short>), dim3((unsigned)ntiles), dim3(256), lds, st,
+                               (const unsigned short *)src, s_row, s_c, src_of, meta, n_rows, C, G.compute, G.units, G.kpad,
+                               dst, (long)G.tile_bytes, MANET_WRONG_LABEL_PADDING_DISTANCE, (unsigned *)nullptr, 0L, 0);
+        return MANET_OK;
+    }
     if (emb_dtype == MANET_EMB_F32)
         hipLaunchKernelGGL((pack_rows_kernel<BT, BT, float>), dim3((unsigned)ntiles), dim3(256), lds, st, (const float *)src,
                            s_row, s_c, src_of, meta, n_rows, C, G.compute, G.units, G.kpad, dst, (long)G.tile_bytes,
@@ -640,6 +724,19 @@ int launch_query_pack(const void *src, int emb_dtype, long s_row, long s_c, long
     constexpr int SR = QB;  // staged rows per workgroup (two blocks per workgroup measured slower: 22 vs 16 us at 480p)
     const size_t lds = (size_t)SR * (G.kpad + 1) * sizeof(float) + 2 * SR * sizeof(int);
     const unsigned blocks = (unsigned)(N_pad / SR);
+    if (emb_dtype != MANET_EMB_F32 && emb_dtype != MANET_EMB_BF16)
+        return manet_set_error(MANET_E_INVALID, "embedding dtype %d (MANET_EMB_F32 / MANET_EMB_BF16)", emb_dtype);
+    if (G.compute == MANET_COMPUTE_F16) {
+        if (emb_dtype == MANET_EMB_F32)
+            hipLaunchKernelGGL((pack_rows_f16_kernel<SR, QB, float>), dim3(blocks), dim3(256), lds, st, (const float *)src, s_row,
+                               s_c, (const int *)nullptr, (const int *)nullptr, N, C, G.compute, G.units, G.kpad, dst,
+                               (long)G.qblk_bytes, 0.0f, keys, N_pad, n_ids);
+        else
+            hipLaunchKernelGGL((pack_rows_f16_kernel<SR, QB, unsigned short>), dim3(blocks), dim3(256), lds, st,
+                               (const unsigned short *)src, s_row, s_c, (const int *)nullptr, (const int *)nullptr, N, C,
+                               G.compute, G.units, G.kpad, dst, (long)G.qblk_bytes, 0.0f, keys, N_pad, n_ids);
+        return MANET_OK;
+    }
     if (emb_dtype == MANET_EMB_F32)
         hipLaunchKernelGGL((pack_rows_kernel<SR, QB, float>), dim3(blocks), dim3(256), lds, st, (const float *)src, s_row, s_c,
                            (const int *)nullptr, (const int *)nullptr, N, C, G.compute, G.units, G.kpad, dst,
@@ -738,7 +835,8 @@ static int frame_prepare_impl(const void *emb, int emb_dtype, int64_t s_f, int64
     A.scale = scale; A.shift = shift; A.relu = relu; A.emb_out = emb_out; A.emb_out_bf16 = (scale && emb_out_dtype == MANET_EMB_BF16) ? 1 : 0;
     // (the epilogue form stores 2-pixel pairs: emb_out rows must pair up as the source's do)
     if (scale && (w & 1)) A.vec2 = 0;
-    A.rcopy = (emb_dtype == MANET_EMB_F32 && G.compute == MANET_COMPUTE_BF16 && !A.emb_out_bf16) ? 1 : 0;
+    const bool f16 = G.compute == MANET_COMPUTE_F16;
+    A.rcopy = (emb_dtype == MANET_EMB_F32 && (G.compute == MANET_COMPUTE_BF16 || f16) && !A.emb_out_bf16) ? 1 : 0;
     const size_t lds = (size_t)(A.rcopy ? 2 : 1) * 2 * XC * (G.kpad + 1) * sizeof(float) + 2 * XC * sizeof(float);
     const dim3 grid((unsigned)(A.n_data + aux), 1, (unsigned)n_frames);
     hipStream_t st = (hipStream_t)stream;

@@ -13,12 +13,15 @@ import torch
 from . import _lib
 
 # "bf16r": bf16 filter + exact fp32 re-rank (MANET_COMPUTE_BF16_REFINE): MANET_COMPUTE_F32's result bit for bit, ~1.4x bf16's cost
+# "f16": fp16 MFMA on embeddings rounded to fp16 (MANET_COMPUTE_F16): bf16's cost, an input-rounding error 8x smaller; values with
+# |row|^2 > 65504 are outside its domain and give NaN (include/manet_hip.h)
 COMPUTE = {"f32": _lib.COMPUTE_F32, "fp32": _lib.COMPUTE_F32, "bf16": _lib.COMPUTE_BF16,
-           "bf16x3": _lib.COMPUTE_BF16X3, "bf16r": _lib.COMPUTE_BF16_REFINE}
+           "bf16x3": _lib.COMPUTE_BF16X3, "bf16r": _lib.COMPUTE_BF16_REFINE, "f16": _lib.COMPUTE_F16, "fp16": _lib.COMPUTE_F16}
 
 
 def _image_kind(compute_code):
-    """operand images depend on the arithmetic only through this: bf16r packs exactly as bf16"""
+    """operand images depend on the arithmetic only through this: bf16r packs exactly as bf16; f16 is a kind of its own (the
+    bf16 image's layout and size with fp16 elements: nothing but this comparison tells the two apart)"""
     return _lib.COMPUTE_BF16 if compute_code == _lib.COMPUTE_BF16_REFINE else compute_code
 
 _ws_cache = {}

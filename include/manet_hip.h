@@ -83,6 +83,16 @@ typedef void *manet_stream_t; /* a hipStream_t */
  * NaN embeddings propagate as in MANET_COMPUTE_F32: a NaN bank row makes its own object's minimum NaN for every query, a NaN
  * query row its own pixel's, every other pair keeps the fp32 bits. */
 #define MANET_COMPUTE_BF16_REFINE 3
+/* v_mfma_f32_32x32x16_f16 on inputs rounded to fp16 (to nearest even, from the fp32 value of an fp32- or bf16-stored embedding),
+ * fp32 accumulate: the reference formula d = |q~|^2 + |k~|^2 - 2 q~.k~ on x~ = fp32(fp16(x)), norms in fp32 from the rounded
+ * values -- MANET_COMPUTE_BF16 with 11 significand bits instead of 8 (an input-rounding error 8x smaller) at the same cost,
+ * workspace sizes and limits (k_nn = 1, every C).  Opt-in; the default stays MANET_COMPUTE_F32.
+ * Domain: fp16 ends at 65504.  A row whose squared norm (of the rounded values) exceeds 65504 -- which covers every element with
+ * |2x| > 65504 -- or that holds an infinity never yields a finite distance: all of ITS distances are NaN.  A query row outside
+ * the domain gives NaN for each of that query's ids, a bank row NaN in its object's column for every query: exactly how a NaN
+ * row propagates, here and in the other modes.  Elements below 2^-14 in magnitude are fp16 subnormals; whether the matrix pipe
+ * keeps or flushes them is the hardware's choice (each such element changes a distance by at most 2 |q~_c| |k~_c|). */
+#define MANET_COMPUTE_F16 4
 
 /* storage type of an embedding operand of the *_ex entry points (take the producer's layout) */
 #define MANET_EMB_F32 0    /* float */
