@@ -1,7 +1,12 @@
-// Geometry of the fused local-window kernel (csrc/local_match.hip) and of the padded pooled planes it reads, shared
-// with the per-frame prepare kernel (csrc/global_prepare.hip: manet_frame_prepare writes those planes and the tile table).
+// Geometry, launch plan and host-side declarations of the local-window stage: csrc/local_fused.hip (the fused kernel and its two
+// halves), csrc/local_match.hip (the unfused kernels of the reference formula) and csrc/local_train.hip (arg-min and backward).
+// The padded pooled planes are shared with the per-frame prepare kernel (csrc/global_prepare.hip: manet_frame_prepare writes those
+// planes and the tile table).  No kernel lives here: a host-only program that includes this header compiles in seconds
+// (tests/test_local_plan.py).
 #pragma once
 #include "manet_common.h"
+#include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -23,6 +28,12 @@ __device__ __forceinline__ Bilin bilin_coeff(int dst, int in_size, int out_size)
     b.l1 = src - (float)a;
     b.l0 = 1.0f - b.l1;
     return b;
+}
+__device__ __forceinline__ float bilin_sample(const float *__restrict__ pl, int wp, const Bilin &by,
+                                              const Bilin &bx)
+{
+    return by.l0 * (bx.l0 * pl[by.i0 * wp + bx.i0] + bx.l1 * pl[by.i0 * wp + bx.i1]) +
+           by.l1 * (bx.l0 * pl[by.i1 * wp + bx.i0] + bx.l1 * pl[by.i1 * wp + bx.i1]);
 }
 // smallest dst in [0, out_size] whose i0 is >= target (i0 is monotone in dst): an estimate from the inverse map,
 // settled with the forward expression itself -- a couple of evaluations instead of a scan over the tile
@@ -132,5 +143,183 @@ static PoolPad lf_pool_pad(int h, int w, int d)
     return G;
 }
 
+// ---- the fused kernel's modes and what travels with them ----
+// MODE (r6): the window distances depend on the two EMBEDDINGS only (IntVOS.py:266-296), the masked minimum (:398-432) on the
+// previous frame's labels -- and a clip's embeddings never change between the interaction rounds of a session (test.py:137-154
+// extracts them once per sequence).  LF_VOL_OUT: phase 1 alone, for a BATCH of frame pairs in one launch (blockIdx.y = pair): each
+// workgroup's normalised volume image -- the exact LDS image phase 2 reads, [ND][SY * 16][VS] floats -- goes to memory.  LF_VOL_IN:
+// phase 2 alone on such an image (one LDS-DMA stream instead of the channel stages): what the sequential chain runs from a
+// clip's second round on.  LF_FUSED: both in one launch, the volume never in memory (r1-r5).  Same arithmetic, same bits.
+constexpr int LF_FUSED = 0, LF_VOL_OUT = 1, LF_VOL_IN = 2;
+constexpr int LF_BATCH = 32;  // frame pairs per LF_VOL_OUT launch (their pointers travel as a kernel argument)
+struct LfBatch {
+    const float *cur[LF_BATCH], *prev[LF_BATCH];
+    float *vol[LF_BATCH];
+};
+// LF_VOL_IN: the tile table (first pixel row / column of every tile) computed on the HOST with the device's expression (fp32 IEEE
+// operations, no contraction: the same integers) and handed over as a kernel argument -- a workgroup's label loads then depend on no
+// memory round trip (under the volume stream the table read alone took 2.5 us, timeline in docs/history/r06_experiments.md)
+constexpr int LF_TAB_MAX = 96;
+struct LfTab {
+    int n;  // entries (nty + 1 + ntx + 1), or 0: read the frame's table from memory
+    int v[LF_TAB_MAX];
+};
+// floats of one workgroup's volume image in memory: the LDS image padded to whole 1 KiB LDS-DMA pieces
+__host__ __device__ constexpr int lf_img_floats(int d) { return (lf_nd(d) * lf_sy(d) * LF_SX * lf_vs(d) + 255) / 256 * 256; }
+// The fp16 image (VT = _Float16, the opt-in storage type of the stored volumes): the SAME [dy][cell of S][dx] order and the same cell
+// stride lf_vs(d) counted in ELEMENTS -- 8 bytes times an odd number, a pixel's taps are ds_read_b64 of 4 window columns and the 16
+// cells of a row of S land on 16 distinct bank pairs.  In memory the images lie back to back WITHOUT the padding to whole pieces
+// (every image is a multiple of 128 bytes; the last piece of a workgroup's fetch reads into the next image, or into the 1 KiB
+// behind the last one, and lands in the padding of the LDS region): exactly half the bytes of the fp32 images' payload.
+template <typename VT>
+__host__ __device__ constexpr int lf_img_elems(int d)
+{
+    return sizeof(VT) == 4 ? lf_img_floats(d) : lf_nd(d) * lf_sy(d) * LF_SX * lf_vs(d);
+}
+
+// ---- tile geometry of local_dist_kernel<D> (csrc/local_match.hip) as a function of the window radius d ----
+constexpr int LD_TX = 16;  // columns per workgroup
+// tile geometry as a function of the window radius d (all compile-time in the kernel):
+__host__ __device__ constexpr int ld_ry(int d)  // grid rows per workgroup: 32 (row, dy) slots
+{
+    return (32 / (2 * d + 1)) < 1 ? 1 : ((32 / (2 * d + 1)) > 8 ? 8 : (32 / (2 * d + 1)));
+}
+__host__ __device__ constexpr int ld_cw(int d) { return (LD_TX + 2 * d + 3) & ~3; }  // halo row stride, 16 B rows
+__host__ __device__ constexpr int ld_yplane(int d) { return (ld_ry(d) + 2 * d) * ld_cw(d); }
+__host__ __device__ constexpr int ld_nj(int d) { return (ld_yplane(d) + 255) / 256; }  // halo elements per thread
+// channels per LDS stage: as many as two stages fit in 64 KiB and ~80 staging registers allow -- a
+// stage costs one global round trip + one barrier, so few, fat stages (4 at d=4, 13 at d=12 for C=100)
+__host__ __device__ constexpr int ld_cc(int d)
+{
+    int by_lds = 65536 / (8 * (ld_yplane(d) + ld_ry(d) * LD_TX));
+    int by_regs = 80 / (ld_nj(d) + 1);
+    int cc = by_lds < by_regs ? by_lds : by_regs;
+    return cc > 25 ? 25 : (cc < 4 ? 4 : cc);
+}
+struct DistLaunch {
+    int RY;
+    dim3 grid;
+    size_t lds;
+};
+static DistLaunch dist_launch(int H, int W, int d)
+{
+    DistLaunch L;
+    int ry = ld_ry(d);  // 256 threads = 32 (row, dy) slots x 8 column pairs
+    L.RY = ry;
+    L.grid = dim3((unsigned)((W + LD_TX - 1) / LD_TX), (unsigned)((H + ry - 1) / ry));
+    L.lds = 2 * (size_t)ld_cc(d) * ((size_t)ld_yplane(d) + (size_t)ry * LD_TX) * sizeof(float);  // 2 stages
+    return L;
+}
+
+// ---- the launch plan of local_fused[_f16]_kernel<D, MODE>: every figure of a launch, of the pooling pass in front of it and of
+// the stored volumes, computed once; the launcher, the entry points and tests/test_local_plan.py all read this ----
+struct LfPlan {
+    int d;
+    PoolPad G;             // the padded pooled planes the kernel stages from
+    int TY, TX, ntx, nty, rw, rh;  // pooled rows / columns of a tile (S without its apron); tiles; tiles per XCD region (4 x 2 regions)
+    unsigned grid_x, grid_y;
+    int nt;                // threads
+    size_t lds, lds_attr;  // dynamic LDS of this launch, and the kernel's attribute (what the largest n_ids needs)
+    long images;           // workgroups (= volume images) of one frame pair
+    int img_elems;         // elements of one image in memory: the kernel's `vimg` stride
+    LfTab tab;             // LF_VOL_IN: the tile table as a kernel argument; n = 0 in the other modes, or when it does not fit
+};
+static LfPlan lf_plan(int h, int w, int d, int mode, int n_ids, size_t elem_bytes, int n_pairs)
+{
+    LfPlan P;
+    P.d = d; P.G = lf_pool_pad(h, w, d);
+    P.TY = lf_sy(d) - 1; P.TX = LF_SX - 1;
+    // i0 runs over 0..hp-1 (the last value only for the last row); tiles cover all of them
+    P.ntx = (P.G.wp + P.TX - 1) / P.TX; P.nty = (P.G.hp + P.TY - 1) / P.TY;
+    P.rw = (P.ntx + 3) / 4; P.rh = (P.nty + 1) / 2;
+    P.grid_x = (unsigned)(8 * P.rw * P.rh * lf_ndg(d)); P.grid_y = (unsigned)(mode == LF_VOL_OUT ? n_pairs : 1);
+    P.nt = lf_nt(d);
+    P.lds = mode == LF_VOL_IN ? lf_lds_vol_bytes(d, n_ids, elem_bytes) : lf_lds_bytes(d);
+    P.lds_attr = mode == LF_VOL_IN ? lf_lds_vol_bytes(d, LF_NIP, elem_bytes) : P.lds;
+    P.images = (long)P.ntx * P.nty * lf_ndg(d);
+    P.img_elems = elem_bytes == 4 ? lf_img_elems<float>(d) : lf_img_elems<_Float16>(d);
+    P.tab.n = 0;
+    if (mode == LF_VOL_IN && P.nty + 1 + P.ntx + 1 <= LF_TAB_MAX) {  // the device's expression on the host: the same integers (lf_pool_pad_kernel / frame prepare)
+        P.tab.n = P.nty + 1 + P.ntx + 1;
+        for (int i = 0; i <= P.nty; ++i) P.tab.v[i] = bilin_first(i * P.TY, P.G.hp, h);
+        for (int i = 0; i <= P.ntx; ++i) P.tab.v[P.nty + 1 + i] = bilin_first(i * P.TX, P.G.wp, w);
+    }
+    return P;
+}
+// bytes of one frame pair's stored volume (+ 1 KiB: the per-pixel kernel fetches whole 1 KiB pieces, past the last image's end)
+static size_t lf_volume_bytes(int h, int w, int d, size_t elem_bytes)
+{
+    const LfPlan P = lf_plan(h, w, d, LF_VOL_OUT, 1, elem_bytes, 1);
+    return (size_t)P.images * P.img_elems * elem_bytes + 1024;
+}
+// the planes of a prepared frame (manet_frame_prepare) are lf_pool_pad's
+static PoolPad pool_pad_of(const ManetFrameLayout &F) { return PoolPad{F.hp, F.wp, F.HPAD, F.WS, F.PS}; }
+
+// f(std::integral_constant<int, D>{}) for the window radius d = D in 0..MANET_MAX_LOCAL_DISTANCE: the one place a runtime radius
+// becomes a kernel's template argument (check_local() rejected every other value already)
+template <class F, int... D>
+void for_window_in(int d, F &&f, std::integer_sequence<int, D...>)
+{
+    (void)((d == D && (f(std::integral_constant<int, D>{}), true)) || ...);
+}
+template <class F>
+void for_window(int d, F &&f) { for_window_in(d, f, std::make_integer_sequence<int, MANET_MAX_LOCAL_DISTANCE + 1>{}); }
+
+// ---- workspaces and argument checks of the entry points ----
+struct LocalLayout {
+    int hp, wp, PP;
+    size_t off_ap, off_bp, off_vol, total;
+};
+LocalLayout local_layout(int h, int w, int C, int d, int downsample)
+{
+    LocalLayout L;
+    L.PP = (2 * d + 1) * (2 * d + 1);
+    L.hp = downsample ? h / 2 : h;
+    L.wp = downsample ? w / 2 : w;
+    size_t plane = (size_t)L.hp * L.wp;
+    // pooled frames: the padded planes of the fused path (the unpadded ones of the other paths fit inside)
+    size_t pooled = downsample ? (size_t)lf_pool_pad(h, w, d).plane * C * sizeof(float) : 0;
+    L.off_ap = 0;
+    L.off_bp = manet_align_up(pooled, 256);
+    L.off_vol = L.off_bp + manet_align_up(pooled, 256);
+    // the volume region doubles as the fused path's tile table (first pixel row / column of every tile)
+    size_t vol = plane * L.PP * sizeof(float), tab = (size_t)(L.hp + L.wp + 4) * sizeof(int);
+    L.total = manet_align_up(L.off_vol + (vol > tab ? vol : tab), 256);
+    return L;
+}
+
+int check_local(int h, int w, int C, int d, int downsample)
+{
+    if (h <= 0 || w <= 0 || C <= 0) return manet_set_error(MANET_E_INVALID, "h=%d w=%d C=%d", h, w, C);
+    if (d < 0 || d > MANET_MAX_LOCAL_DISTANCE)
+        return manet_set_error(MANET_E_INVALID, "max_distance=%d (supported 0..%d)", d, MANET_MAX_LOCAL_DISTANCE);
+    if (downsample && (h < 2 || w < 2)) return manet_set_error(MANET_E_INVALID, "downsample needs h,w >= 2");
+    return MANET_OK;
+}
+int check_ids(int n_ids)
+{
+    if (n_ids <= 0 || n_ids > MANET_MAX_IDS)
+        return manet_set_error(MANET_E_INVALID, "n_ids=%d (supported 1..%d)", n_ids, MANET_MAX_IDS);
+    return MANET_OK;
+}
+// manet_local_match_backward_f32: four pooled frames (both inputs, both gradients), then the volume's gradient
+static size_t local_bwd_ws_bytes(int h, int w, int C, int d)
+{
+    size_t plane = (size_t)(h / 2) * (w / 2), PP = (size_t)(2 * d + 1) * (2 * d + 1);
+    return manet_align_up(4 * plane * C * sizeof(float), 256) + manet_align_up(plane * PP * sizeof(float), 256);
+}
 
 }  // namespace
+
+// Host functions one local file offers the others (every kernel is emitted by exactly one file).  csrc/local_match.hip:
+// local_dist_kernel<d>; and pool2x2_kernel of both frames into ap / bp [C][hp][wp], then -- vol != nullptr -- their normalised volume
+void manet_local_launch_dist(int d, hipStream_t st, const float *x, long x_sy, long x_sx, long x_sc, const float *y, long y_sy,
+                             long y_sx, long y_sc, int H, int W, int C, int pooled_out, float *out);
+void manet_local_pooled_volume(const float *cur, long c_sy, long c_sx, long c_sc, const float *prev, long p_sy, long p_sx, long p_sc,
+                               int C, int hp, int wp, int d, float *ap, float *bp, float *vol, hipStream_t st);
+// csrc/local_fused.hip: the pooling pass + the fused kernel (`pooled`: room for the two padded pooled frames, 2 * C *
+// lf_pool_pad().plane floats; `tab`: the tile table); and fill_f32_kernel with zeros in at most 2048 blocks (the backwards)
+void manet_local_launch_fused(int d, hipStream_t st, const void *cur, long c_sy, long c_sx, long c_sc, const void *prev, long p_sy,
+                              long p_sx, long p_sc, int emb_dtype, const int *labels, int h, int w, int C, int n_ids, float *out,
+                              float *pooled, int *tab);
+void manet_local_fill_zero(float *p, long n, hipStream_t st);

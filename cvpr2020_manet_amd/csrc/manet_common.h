@@ -43,7 +43,7 @@ enum { MANET_TUNE_BLOCK_MAP = 0, MANET_TUNE_SPLITS = 1, MANET_TUNE_LOCAL_UNFUSED
 int manet_tune_get(int key, int dflt);
 
 // csrc/match_train.hip: masked minimum + winning window offset of the training forward on a normalised pooled volume
-// [(2d+1)^2][hp][wp] (the tail of manet_local_match_train_forward_f32; local_min_arg_kernel's bits)
+// [(2d+1)^2][hp][wp] (the tail of csrc/local_train.hip's manet_local_match_train_forward_f32; local_min_arg_kernel's bits)
 void manet_mt_launch_local_min_arg(const float *vol, const int32_t *labels, int h, int w, int hp, int wp, int d, int n_ids,
                                    float *out, int32_t *arg, hipStream_t st);
 
@@ -51,7 +51,7 @@ static inline size_t manet_align_up(size_t x, size_t a) { return (x + a - 1) / a
 
 // Per-frame operands written by manet_frame_prepare (csrc/global_prepare.hip), read by manet_global_match_prepared_ex
 // (csrc/global_match.hip: the query operand image, at offset 0: a frame workspace IS a MANET_EMB_PACKED query) and by manet_local_match_frames
-// (csrc/local_match.hip: the 2x2-average-pooled plane with its border of the reference's padding value, and the tile
+// (csrc/local_fused.hip: the 2x2-average-pooled plane with its border of the reference's padding value, and the tile
 // table of the fused kernel).  max_distance < 0: no pooled plane (global match only).
 struct ManetFrameLayout {
     size_t off_image, image_bytes, off_plane, plane_bytes, off_tab, tab_bytes, total;

@@ -18,7 +18,7 @@ struct Bil {
     int i0, i1;
     float l0, l1;
 };
-// aten area_pixel_compute_scale (align_corners=True) + linear source index, as in local_match.hip
+// aten area_pixel_compute_scale (align_corners=True) + linear source index, as in local_geom.h
 __device__ __forceinline__ Bil bil(int dst, int in_size, int out_size)
 {
     float scale = (out_size > 1) ? (float)(in_size - 1) / (float)(out_size - 1) : 0.0f;

@@ -1,7 +1,7 @@
 // Ordered (atomic-free) backward of the matching path, MI355X (gfx950): the opt-in training route behind
 // ops.global_match / ops.local_match(deterministic=True) and IntVOS(train_match="ordered").
 //
-// The default route (csrc/global_match.hip global_match_backward_kernel, csrc/local_match.hip local_bwd_scatter*_kernel) adds
+// The default route (csrc/global_match.hip global_match_backward_kernel, csrc/local_train.hip local_bwd_scatter*_kernel) adds
 // colliding contributions with float atomicAdd: the sum depends on arrival order and its last bits change from run to run.
 // Here every sum has ONE owner that adds its terms in an order fixed by indices alone, so the gradients are the same bits on
 // every run.  No float atomic anywhere in this file (tests/test_match_train_abi.py reads the device assembly).
@@ -695,7 +695,7 @@ int mt_check_global(int64_t N, int64_t M0, int C, int n_ids, int ranks)
 
 }  // namespace
 
-// the tail of manet_local_match_train_forward_f32 (csrc/local_match.hip, which owns the pooling and distance kernels in front of it)
+// the tail of manet_local_match_train_forward_f32 (csrc/local_train.hip; csrc/local_match.hip owns the pooling and distance kernels in front of it)
 void manet_mt_launch_local_min_arg(const float *vol, const int32_t *labels, int h, int w, int hp, int wp, int d, int n_ids,
                                    float *out, int32_t *arg, hipStream_t st)
 {

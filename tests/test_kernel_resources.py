@@ -16,7 +16,7 @@ import pytest
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "cvpr2020_manet_amd", "csrc")
-FILES = ["global_match.hip", "global_prepare.hip", "global_refine.hip", "local_match.hip", "seg_head.hip", "mask_step.hip", "correlation.hip"]
+FILES = ["global_match.hip", "global_prepare.hip", "global_refine.hip", "local_fused.hip", "local_match.hip", "local_train.hip", "seg_head.hip", "mask_step.hip", "correlation.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c"]
 

@@ -18,7 +18,7 @@ def f16_kernels():
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")
     out = {}
-    for mangled, row in tkr._report("local_match.hip").items():
+    for mangled, row in tkr._report("local_fused.hip").items():
         m = re.search(r"local_fused_f16_kernelILi(\d+)ELi(\d+)EE", mangled)
         if m:
             out[(int(m.group(1)), int(m.group(2)))] = row

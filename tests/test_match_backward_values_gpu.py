@@ -1,5 +1,5 @@
 """GPU: the VALUES of the matching path's backward, both routes -- the float-atomic kernels (csrc/global_match.hip,
-csrc/local_match.hip) and the ordered, atomic-free ones (csrc/match_train.hip) -- against the float64 restatements of
+csrc/local_train.hip) and the ordered, atomic-free ones (csrc/match_train.hip) -- against the float64 restatements of
 tests/match_grad_ref.py (held to the reference's own autograd by tests/test_match_grad_ref.py), at the shapes where a kernel
 can be wrong with the same bits on every run.  Every case runs deterministic=False and deterministic=True through
 ops.global_match / ops.local_match and takes the selection from the op's saved tensors.
