@@ -144,11 +144,13 @@ SIGNATURES = {
                                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
-COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X3, COMPUTE_BF16_REFINE, COMPUTE_F16 = 0, 1, 2, 3, 4
+COMPUTE_F32, COMPUTE_BF16, COMPUTE_BF16X3, COMPUTE_BF16_REFINE, COMPUTE_F16, COMPUTE_F16_REFINE = 0, 1, 2, 3, 4, 6
+REFINE_MODES = (COMPUTE_BF16_REFINE, COMPUTE_F16_REFINE)  # filter + exact fp32 re-rank: MANET_COMPUTE_F32's bits
 EMB_F32, EMB_BF16, EMB_PACKED = 0, 1, 2
 EPI_NORMALIZE = 1
 EPI_KEYS_ARMED = 2
 EPI_REFINE_EXACT = 4
+EPI_REFINE_F16 = 8  # manet_global_match_refine: the bank / image are MANET_COMPUTE_F16_REFINE's
 
 _lib = None
 

@@ -971,7 +971,7 @@ __device__ __forceinline__ void plain_wide_body(const char *__restrict__ qpack,
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31;
+    int l31 = lane & 31;
     const int h = lane >> 5;
 
     int qt, s, t0, t1;
@@ -1336,6 +1336,9 @@ __device__ __forceinline__ void plain_wide_body(const char *__restrict__ qpack,
             }
         }
     }
+    // (the fp16 filter: the lane's query column of the closing test is taken from the lane id again, not carried through the
+    // step loop -- there every register is taken, and global_match_bf16_wide_kernel<7, true> spills exactly this value around it)
+    if constexpr (FILTER && std::is_same<E, ElemF16>::value) l31 = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 31;
     test_pending();
 #undef MANET_PASS
 #undef MANET_PASS_F
@@ -1366,7 +1369,7 @@ __global__ __launch_bounds__(256, 2) void global_match_bf16_wide_kernel(const ch
     plain_wide_body<KSB, FILTER, ElemBF16>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, block_map, thr, slack, stats, list,
                                            bucket_cap, bcnt);
 }
-// MANET_COMPUTE_F16, C <= 106: the plain form only (the filter form is MANET_COMPUTE_BF16_REFINE's, bf16)
+// MANET_COMPUTE_F16, C <= 106, and the pre-pass of MANET_COMPUTE_F16_REFINE: the plain form (the filter form: refine_filter_half_kernel)
 template <int KSB>
 __global__ __launch_bounds__(256, 2) void f16_match_wide_kernel(const char *__restrict__ qpack, const char *__restrict__ bpack,
                                                                 const int *__restrict__ meta, int n_ids, int nQT, int S, long N_pad,
@@ -1374,6 +1377,28 @@ __global__ __launch_bounds__(256, 2) void f16_match_wide_kernel(const char *__re
 {
     plain_wide_body<KSB, false, ElemF16>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, block_map, nullptr, nullptr, nullptr, nullptr,
                                          0L, nullptr);
+}
+// MANET_COMPUTE_F16_REFINE: the FILTER form on fp16 images, with global_match_bf16_wide_kernel<KSB, true>'s arguments.  The body
+// has one fp16-only line (the closing test's lane column, a register matter); what differs from bf16 in VALUES is met as it stands:
+//   * a tile's padding rows give +inf, not 1e20: a pass of padding alone has the minimum +inf, which tightens nothing
+//     (fminf(tq, inf + slack) = tq) and is below no threshold (thresholds of in-domain pairs are finite);
+//   * a row outside fp16's domain (bank or query) gives NaN distances: min3p carries a NaN into the pass's minimum, fminf drops it
+//     from the tightening, `NaN <= tq` lists nothing -- the NaN may HIDE the other 15 rows of its lane's pass, so every pair such
+//     a row takes part in must reach the exact route.  refine_threshold_f16_kernel (csrc/global_refine.hip) marks the query
+//     blocks of out-of-domain queries incomplete; out-of-domain BANK rows (META_F16_OOD) concern every query, all tiles are
+//     rescued, and nothing this kernel could list would be read: it returns at once.
+template <int KSB>
+__global__ __launch_bounds__(256, 2) void refine_filter_half_kernel(const char *__restrict__ qpack, const char *__restrict__ bpack,
+                                                                    const int *__restrict__ meta, int n_ids, int nQT, int S,
+                                                                    long N_pad, unsigned *__restrict__ keys, int block_map,
+                                                                    unsigned *__restrict__ thr, const float *__restrict__ slack,
+                                                                    unsigned long long *__restrict__ stats,
+                                                                    uint2 *__restrict__ list, long bucket_cap,
+                                                                    unsigned *__restrict__ bcnt)
+{
+    if (meta[META_F16_OOD]) return;  // (uniform)
+    plain_wide_body<KSB, true, ElemF16>(qpack, bpack, meta, n_ids, nQT, S, N_pad, keys, block_map, thr, slack, stats, list,
+                                        bucket_cap, bcnt);
 }
 
 #undef MANET_MFMA
@@ -1525,7 +1550,8 @@ __global__ void zero_strided_kernel(float *__restrict__ p, long n0, long n1, lon
 // rescue: by its caller).  The LDS attribute is set per call (cheap, host side): it is per device and the library keeps no state.
 //   plain bf16 -> global_match_bf16_wide_kernel (k-steps 2 / 7), global_match_bf16_pipe_kernel for C > 106 (k-step 9: its
 //   144 operand VGPRs do not fit the wide form; MANET_COMPUTE_BF16_REFINE supports C <= 106); split-bf16 -> the x3 kernel;
-//   MANET_COMPUTE_F16 -> the fp16 wrappers of the same two bodies, f16_match_wide_kernel<2 / 7> and f16_match_pipe_kernel<9>
+//   MANET_COMPUTE_F16 -> the fp16 wrappers of the same two bodies, f16_match_wide_kernel<2 / 7> and f16_match_pipe_kernel<9>;
+//   MANET_COMPUTE_F16_REFINE -> f16_match_wide_kernel (pre-pass) and refine_filter_half_kernel (filter), k-steps 2 / 7
 void launch_match(const MatchPlan &P, const MatchArgs &A, hipStream_t st)
 {
     const bool rescue = P.form == MATCH_FORM_REFINE_RESCUE || P.form == MATCH_FORM_REFINE_RESCUE_EXACT;
@@ -1552,6 +1578,12 @@ void launch_match(const MatchPlan &P, const MatchArgs &A, hipStream_t st)
             if (P.compute == MANET_COMPUTE_BF16X3) go(global_match_bf16x3_kernel<K>, 512, A.keys, P.block_map);
             else if (P.compute == MANET_COMPUTE_F16) {  // (k-step 9 -- C > 106 -- takes the narrow form, as plain bf16)
                 if constexpr (K == 9) go(f16_match_pipe_kernel<K>, 512, A.keys, P.block_map);
+                else go(f16_match_wide_kernel<K>, 256, A.keys, P.block_map);
+            }
+            else if (P.compute == MANET_COMPUTE_F16_REFINE) {  // (C <= 106: check_common; the pre-pass is the plain fp16 kernel)
+                if constexpr (K == 9) return;
+                else if (P.form == MATCH_FORM_REFINE_FILTER)
+                    go(refine_filter_half_kernel<K>, 256, A.keys, P.block_map, A.thr, A.slack, A.stats, A.list, A.bucket_cap, A.bcnt);
                 else go(f16_match_wide_kernel<K>, 256, A.keys, P.block_map);
             }
             else if constexpr (K == 9) go(global_match_bf16_pipe_kernel<K>, 512, A.keys, P.block_map);
@@ -1631,11 +1663,12 @@ int manet_global_match_prepared_ex(const void *query, int emb_dtype, int64_t q_s
     } else if (!armed) {
         fill32(keys, 0xffffffffu, (size_t)n_ids * ML.N_pad, st);
     }
-    if (compute == MANET_COMPUTE_BF16_REFINE) {
+    if (is_refine(compute)) {
         if (emb_dtype == MANET_EMB_PACKED)
-            return manet_set_error(MANET_E_INVALID, "MANET_COMPUTE_BF16_REFINE re-ranks in fp32 from the query as stored: pass "
-                                                    "it to manet_global_match_refine next to its packed image");
-        return run_refine(qpack, query, emb_dtype, (long)q_stride_n, (long)q_stride_c, bws, BL, mws, ML, (long)N, M0, C, n_ids, out,
+            return manet_set_error(MANET_E_INVALID, "MANET_COMPUTE_%s_REFINE re-ranks in fp32 from the query as stored: pass "
+                                                    "it to manet_global_match_refine next to its packed image",
+                                   compute == MANET_COMPUTE_F16_REFINE ? "F16" : "BF16");
+        return run_refine(compute, qpack, query, emb_dtype, (long)q_stride_n, (long)q_stride_c, bws, BL, mws, ML, (long)N, M0, C, n_ids, out,
                           mem_inout, epilogue_flags, st);
     }
     const char *bpack = bws + BL.off_pack;

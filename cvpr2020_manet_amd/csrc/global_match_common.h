@@ -16,6 +16,10 @@ constexpr int META_T = 0;          // [0]        number of bank tiles actually u
 constexpr int META_SEG = 1;        // [1..65]    first tile of object o (entry n_ids = T)
 constexpr int META_CNT = 130;      // [130..193] rows per object
 constexpr int META_KMAX = 200;     // [200]      max |k|^2 over the bank's rows, float bits (MANET_COMPUTE_BF16_REFINE)
+// MANET_COMPUTE_F16_REFINE, from the bank's fp16 image itself (f16_domain_kernel, csrc/global_prepare.hip):
+constexpr int META_F16_KMAX = 201;  // [201]     max |k~|^2 over the rows INSIDE fp16's domain, float bits
+constexpr int META_F16_SUBN = 202;  // [202]     max over those rows of the number of elements that are nonzero fp16 subnormals
+constexpr int META_F16_OOD = 203;   // [203]     != 0: an object without a NaN row holds a row outside fp16's domain
 // MANET_COMPUTE_BF16_REFINE: a pre-pass over every REFINE_SUB-th bank tile gives an upper bound of the minimum; the full
 // bf16 pass then keeps, per (query, object), the bank rows that could beat it; up to REFINE_CAP of them are re-evaluated in
 // the reference's fp32 arithmetic
@@ -123,7 +127,7 @@ struct BankLayout {
     long T_max;  // upper bound on tiles: every object wastes < 1 tile
     long nblocks;  // pre-pass blocks of RPB rows
     size_t off_meta, off_hist, off_src, off_pack, total;
-    // MANET_COMPUTE_BF16_REFINE only: the sorted rows once more in fp32, row-major [T_max * 64][C] + their |k|^2 (what the
+    // MANET_COMPUTE_BF16_REFINE / _F16_REFINE only: the sorted rows once more in fp32, row-major [T_max * 64][C] + their |k|^2 (what the
     // exact re-rank reads), and the sub-sampled bank of the pre-pass (its own meta block + every REFINE_SUB-th tile)
     long T_sub_max;
     size_t off_rows, off_norms, off_sub_meta, off_sub_pack;
@@ -149,8 +153,8 @@ enum MatchForm {
     MATCH_FORM_MAIN = 0,             // manet_global_match_prepared_ex: fp32 pipe / general fp32 (k_nn > 1) / bf16 wide, pipe, x3
     MATCH_FORM_ARG,                  // the arg-min form of the general fp32 kernel
     MATCH_FORM_NTH_ARG,              // ... and its bounded form (pass j of the k nearest rows): the same plan
-    MATCH_FORM_REFINE_PRE,           // MANET_COMPUTE_BF16_REFINE: the pre-pass over the sub-sampled bank (bf16 wide),
-    MATCH_FORM_REFINE_FILTER,        // ... the filter pass (bf16 wide, FILTER; spread / tapered map),
+    MATCH_FORM_REFINE_PRE,           // MANET_COMPUTE_BF16_REFINE / _F16_REFINE: the pre-pass over the sub-sampled bank (bf16 / fp16 wide),
+    MATCH_FORM_REFINE_FILTER,        // ... the filter pass (the wide body's FILTER form; spread / tapered map),
     MATCH_FORM_REFINE_RESCUE,        // ... the rescue of the listed query tiles (fp32 pipe, RESCUE)
     MATCH_FORM_REFINE_RESCUE_EXACT,  // ... or of every tile (MANET_EPI_REFINE_EXACT)
 };
@@ -185,10 +189,14 @@ struct MatchArgs {  // the main kernels' arguments next to the plan's; from `thr
 
 namespace {
 
+// the two filter + exact fp32 re-rank modes: one set of layouts, plans and limits (the images are the same size)
+constexpr bool is_refine(int compute) { return compute == MANET_COMPUTE_BF16_REFINE || compute == MANET_COMPUTE_F16_REFINE; }
+
 Geom geom_of(int C, int compute)
 {
     Geom G;
     if (compute == MANET_COMPUTE_BF16_REFINE) compute = MANET_COMPUTE_BF16;  // same operand images as plain bf16
+    if (compute == MANET_COMPUTE_F16_REFINE) compute = MANET_COMPUTE_F16;    // ... and as plain fp16
     G.compute = compute;  // (MANET_COMPUTE_F16 stays: the bf16 image's geometry, fp16 elements)
     if (compute == MANET_COMPUTE_F32) {
         G.steps = pick_ks(C);
@@ -224,7 +232,7 @@ BankLayout bank_layout(int64_t M0, int C, int n_ids, int compute)
     L.T_sub_max = 0;
     L.off_rows = L.off_norms = L.off_sub_meta = L.off_sub_pack = L.off_pack32 = 0;
     L.G32 = L.G;
-    if (compute == MANET_COMPUTE_BF16_REFINE) {
+    if (is_refine(compute)) {
         L.T_sub_max = L.T_max / refine_sub(L.T_max) + n_ids + 1;
         L.off_rows = L.total;
         L.off_norms = manet_align_up(L.off_rows + (size_t)L.T_max * BT * C * sizeof(float), 256);
@@ -256,7 +264,7 @@ MatchLayout match_layout(int64_t N, int C, int n_ids, int compute, int k_nn = 1,
         L.total = manet_align_up(L.off_topk + (size_t)n_ids * L.N_pad * sizeof(unsigned long long), 1024);
     L.off_thr = L.off_slack = L.off_keys2 = L.off_list = L.off_stats = L.off_bcnt = L.off_q32 = 0;
     L.list_cap = L.bucket_cap = 0;
-    if (compute == MANET_COMPUTE_BF16_REFINE) {
+    if (is_refine(compute)) {
         const size_t pairs = (size_t)n_ids * L.N_pad;
         L.list_cap = (long)pairs * REFINE_CAP;
         L.off_thr = L.off_topk;
@@ -317,10 +325,13 @@ int check_common(int64_t N, int64_t M0, int C, int n_ids, int k_nn, int compute)
     if (k_nn > 1 && compute != MANET_COMPUTE_F32)
         return manet_set_error(MANET_E_INVALID, "k_nn > 1 needs MANET_COMPUTE_F32");
     if (compute != MANET_COMPUTE_F32 && compute != MANET_COMPUTE_BF16 && compute != MANET_COMPUTE_BF16X3 &&
-        compute != MANET_COMPUTE_BF16_REFINE && compute != MANET_COMPUTE_F16)
-        return manet_set_error(MANET_E_INVALID, "compute=%d (MANET_COMPUTE_F32 / _BF16 / _BF16X3 / _BF16_REFINE / _F16)", compute);
+        compute != MANET_COMPUTE_BF16_REFINE && compute != MANET_COMPUTE_F16 && compute != MANET_COMPUTE_F16_REFINE)
+        return manet_set_error(MANET_E_INVALID, "compute=%d (MANET_COMPUTE_F32 / _BF16 / _BF16X3 / _BF16_REFINE / _F16 / _F16_REFINE)",
+                               compute);
     if (compute == MANET_COMPUTE_BF16_REFINE && C + BF16_SPECIAL > 112)
         return manet_set_error(MANET_E_INVALID, "MANET_COMPUTE_BF16_REFINE supports C <= 106 (the wide bf16 kernel)");
+    if (compute == MANET_COMPUTE_F16_REFINE && C + BF16_SPECIAL > 112)
+        return manet_set_error(MANET_E_INVALID, "MANET_COMPUTE_F16_REFINE supports C <= 106 (the wide fp16 kernel)");
     return MANET_OK;
 }
 
@@ -356,7 +367,7 @@ MatchTune match_tune()
     return {manet_tune_get(MANET_TUNE_SPLITS, 0), manet_tune_get(MANET_TUNE_BLOCK_MAP, -1), manet_tune_get(MANET_TUNE_ONE_ROUND, 0)};
 }
 
-// `compute` is MANET_COMPUTE_BF16_REFINE for the refine forms and MANET_COMPUTE_F32 for the arg forms.
+// `compute` is MANET_COMPUTE_BF16_REFINE / _F16_REFINE for the refine forms and MANET_COMPUTE_F32 for the arg forms.
 MatchPlan match_plan(int64_t N, int64_t M0, int C, int n_ids, int k_nn, int compute, int form, const MatchTune &tune)
 {
     const BankLayout BL = bank_layout(M0, C, n_ids, compute);
@@ -498,11 +509,12 @@ int launch_bank_pack(const void *src, int emb_dtype, long s_row, long s_c, const
 int launch_query_pack(const void *src, int emb_dtype, long s_row, long s_c, long N, long N_pad, int C, const Geom &G,
                       char *dst, unsigned *keys, int n_ids, hipStream_t st);
 // csrc/global_refine.hip (called by manet_global_match_prepared_ex):
-int run_refine(const char *qimg, const void *qraw, int q_dtype, long q_sn, long q_sc, const char *bws, const BankLayout &BL,
-               char *mws, const MatchLayout &ML, long N, int64_t M0, int C, int n_ids, float *out, float *mem, int flags,
-               hipStream_t st);
+int run_refine(int compute, const char *qimg, const void *qraw, int q_dtype, long q_sn, long q_sc, const char *bws,
+               const BankLayout &BL, char *mws, const MatchLayout &ML, long N, int64_t M0, int C, int n_ids, float *out, float *mem,
+               int flags, hipStream_t st);
 // csrc/global_match.hip: the main kernel of the plan's form -- how run_refine reaches the three kernels it borrows, the pre-pass
-// (bf16_wide<K, false>), the filter (bf16_wide<K, true>) and the rescue (f32_pipe<KS, true>) -- and the closing decode
+// (bf16_wide<K, false> / f16_match_wide), the filter (bf16_wide<K, true> / refine_filter_half) and the rescue (f32_pipe<KS, true>)
+// -- and the closing decode
 void launch_match(const MatchPlan &P, const MatchArgs &A, hipStream_t st);
 void launch_global_finish(unsigned *keys, long N, long N_pad, int n_ids, int flags, float *out, float *mem, long total,
                           hipStream_t st);

@@ -648,6 +648,60 @@ __global__ __launch_bounds__(256) void bank_rows_f32_kernel(const SRC *__restric
     }
 }
 
+// MANET_COMPUTE_F16_REFINE: what the filter's threshold must know about the bank, read from the packed fp16 image ITSELF (so that
+// "outside the domain" here is exactly "NaN in the norm slot" there); a wave per tile, a lane per row:
+//   META_F16_KMAX  max |k~|^2 over the rows inside fp16's domain (the scaled norm pieces of slots C .. C+2, see the f16 image)
+//   META_F16_SUBN  max over those rows of the number of elements that are nonzero fp16 subnormals
+//   META_F16_OOD   set if a row is outside the domain (NaN in its first norm slot) and its object holds no NaN row (META_NAN,
+//                  written by bank_rows_f32_kernel before this launch: a NaN object's minimum is NaN whatever else it holds)
+// Padding rows (+inf in the first norm slot) count for nothing.
+__global__ __launch_bounds__(64) void f16_domain_kernel(const char *__restrict__ bpack, long tile_bytes, int units, int C,
+                                                        int *__restrict__ meta)
+{
+    const long tile = blockIdx.x;
+    if (tile >= meta[META_T]) return;
+    const int r = threadIdx.x;
+    const char *img = bpack + tile * tile_bytes;
+    auto elem = [&](int k) {
+        const int u = 2 * (k >> 4) + ((k >> 3) & 1);
+        return (unsigned)*(const unsigned short *)(img + ((long)u * BT + r) * 16 + (k & 7) * 2);
+    };
+    const unsigned p0 = elem(C), a0 = p0 & 0x7fffu;
+    const bool ood = a0 > 0x7c00u, real = a0 < 0x7c00u;
+    float n2 = 0.0f;
+    int sub = 0;
+    if (real) {
+        n2 = h2f(p0) + h2f(elem(C + 1)) * (1.0f / 2048.0f) + h2f(elem(C + 2)) * (1.0f / 16384.0f);
+        for (int u = 0; u < units; ++u) {
+            const uint4 v = *(const uint4 *)(img + ((long)u * BT + r) * 16);
+            const unsigned w[4] = {v.x, v.y, v.z, v.w};
+            const int k0 = 16 * (u >> 1) + 8 * (u & 1);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const unsigned b = (w[e >> 1] >> (16 * (e & 1))) & 0x7fffu;
+                sub += (k0 + e < C && b != 0u && b < 0x0400u) ? 1 : 0;
+            }
+        }
+    }
+    unsigned nb = __float_as_uint(n2);  // n2 >= 0: the bit pattern orders like the value
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned onb = (unsigned)__shfl_xor((int)nb, d);
+        const int osub = __shfl_xor(sub, d);
+        nb = onb > nb ? onb : nb;
+        sub = osub > sub ? osub : sub;
+    }
+    const bool any_ood = __ballot(ood) != 0ull;
+    if (r == 0) {
+        atomicMax((unsigned *)&meta[META_F16_KMAX], nb);
+        atomicMax(&meta[META_F16_SUBN], sub);
+        if (any_ood) {
+            int o = 0;
+            while (meta[META_SEG + o + 1] <= tile) ++o;
+            if (!meta[META_NAN + o]) meta[META_F16_OOD] = 1;
+        }
+    }
+}
+
 // sub-sampled bank of the pre-pass: every REFINE_SUB-th tile of every object (at least one per non-empty object)
 __global__ void sub_segments_kernel(int n_ids, const int *__restrict__ meta, int *__restrict__ sub_meta, int REFINE_SUB)
 {
@@ -814,7 +868,7 @@ static int frame_prepare_impl(const void *emb, int emb_dtype, int64_t s_f, int64
     FramePrep A;
     A.emb = emb;
     A.s_f = (long)s_f; A.s_y = (long)s_y; A.s_x = (long)s_x; A.s_c = (long)s_c;
-    A.h = h; A.w = w; A.C = C; A.compute = G.compute; A.units = G.units; A.kpad = G.kpad;  // (G.compute: _BF16_REFINE packs as _BF16)
+    A.h = h; A.w = w; A.C = C; A.compute = G.compute; A.units = G.units; A.kpad = G.kpad;  // (G.compute: _BF16_REFINE packs as _BF16, _F16_REFINE as _F16)
     A.ws = (char *)frames_ws; A.ws_stride = (long)frame_ws_stride; A.qblk_bytes = (long)G.qblk_bytes;
     A.off_plane = (long)F.off_plane; A.off_tab = (long)F.off_tab;
     A.d = max_distance; A.hp = F.hp; A.wp = F.wp; A.HPAD = F.HPAD; A.WS = F.WS; A.PS = F.PS;
@@ -919,7 +973,7 @@ int manet_bank_prepare_ex(const void *bank, int emb_dtype, int64_t b_stride_m, i
     rc = launch_bank_pack(bank, emb_dtype, (long)b_stride_m, (long)b_stride_c, (const int *)src_of, (const int *)meta, (long)M0,
                           C, L.G, ws + L.off_pack, L.T_max, st);
     if (rc) return rc;
-    if (compute == MANET_COMPUTE_BF16_REFINE) {
+    if (is_refine(compute)) {
         // the fp32 operand image of the same sorted bank: what the rescue pass (the exact fp32 kernel on the query blocks
         // whose candidate buckets are incomplete) multiplies against
         rc = launch_bank_pack(bank, emb_dtype, (long)b_stride_m, (long)b_stride_c, (const int *)src_of, (const int *)meta,
@@ -936,6 +990,9 @@ int manet_bank_prepare_ex(const void *bank, int emb_dtype, int64_t b_stride_m, i
                 hipLaunchKernelGGL(bank_rows_f32_kernel<unsigned short>, dim3((unsigned)L.T_max), dim3(256), 0, st,
                                    (const unsigned short *)bank, (long)b_stride_m, (long)b_stride_c, (const int *)src_of, meta, C,
                                    rows, norms);
+            if (compute == MANET_COMPUTE_F16_REFINE)
+                hipLaunchKernelGGL(f16_domain_kernel, dim3((unsigned)L.T_max), dim3(64), 0, st, (const char *)(ws + L.off_pack),
+                                   (long)L.tile_bytes, L.G.units, C, meta);
         }
         fill32(sub_meta, 0u, META_INTS, st);
         const int sub = refine_sub(L.T_max);

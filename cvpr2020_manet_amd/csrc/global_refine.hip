@@ -1,4 +1,4 @@
-// Global nearest-neighbour matching, MANET_COMPUTE_BF16_REFINE.  The threshold, re-rank and statistics kernels live here; the
+// Global nearest-neighbour matching, MANET_COMPUTE_BF16_REFINE and MANET_COMPUTE_F16_REFINE.  The threshold, re-rank and statistics kernels live here; the
 // pre-pass, the filter and the rescue are forms of the main kernels, launched through launch_match (csrc/global_match.hip).
 //
 // MANET_COMPUTE_BF16_REFINE: fp32-exact minima at bf16 cost (VERDICT r2 "next" #4).
@@ -17,6 +17,27 @@
 // plus the fp32 accumulation error of either evaluation (a = 8 (C + 8) 2^-24 s^2, generous).  For the two rows that matter
 // (the pre-pass's best row and the true arg-min) d <= U + E0 + a with the crude E0 = (2u + u^2) s^2 + a, hence
 //   E = 2 u s sqrt(max(U, 0) + E0 + a) + u^2 s^2 + a   bounds both, and thr = U + 2 E (x 1.05 against the bound's own rounding).
+//
+// MANET_COMPUTE_F16_REFINE: the same five steps with the pre-pass and the filter in fp16 arithmetic on the fp16 images (the
+// re-rank, the rescue and the statistics are shared).  Its bound, with u = 2^-11 (fp16 round-to-nearest) -- the threshold's leading
+// term 2 u s sqrt(U) is 8x bf16's true one (bf16's u is 2^-8; the 2^-9 above is carried by the crude s and the 2.1):
+//   Elements.  x~ = fp16(x).  A NORMAL x~ has |x~ - x| <= u |x|.  An x~ that is zero or subnormal has |x~ - x| <= 2^-25.  The
+//   matrix pipe may keep a nonzero subnormal operand or flush it to zero (the project leaves that open): the operand it USES, x^,
+//   then differs from x by less than 2^-14.  (The query image holds -2 q~, a subnormal of which comes from a subnormal q~.)
+//   With n_q = the number of nonzero subnormal elements of the rounded query row, n_k = the maximum of that count over the bank's
+//   in-domain rows, and e = (q^ - q) - (k^ - k):
+//     |e| <= u (|q| + |k|) + 2^-14 (sqrt(n_q) + sqrt(n_k)) + 2^-24 sqrt(C)                                   =: eps
+//   Distances.  The MFMA chain gives |q~|^2 + |k~|^2 - 2 q^.k^: the norm slots hold the norms of the ROUNDED rows, flushed or
+//   not.  q~ = q^ + f_q with f_q the flushed elements (disjoint support, |f_q|^2 <= 2^-28 n_q), so this is
+//     |q^ - k^|^2 + |f_q|^2 + |f_k|^2,   and   |q^ - k^|^2 - |q - k|^2 = 2 (q - k).e + |e|^2:
+//     | d~ - d | <= 2 sqrt(d) eps + eps^2 + 2^-28 (n_q + n_k) + 2 * 2^-28 + a <= 2 sqrt(d) eps + 2 eps^2 + 2^-27 + a
+//   (2^-28 (n_q + n_k) <= eps^2; 2^-28 per side: what the scaled norm pieces drop of a norm below 2^-5, global_match_common.h;
+//   a = 8 (C + 8) 2^-24 s^2 as above, the fp32 accumulation of either evaluation).  s = |q| + max |k| >= sqrt(d) gives the crude
+//   E0 = 2 s eps + 2 eps^2 + 2^-27 + a, and, as above, for the two rows that matter
+//     E = 2 eps sqrt(max(U, 0) + E0 + a) + 2 eps^2 + 2^-27 + a,   thr = U + 2 E (x 1.05).
+//   |q|, |k| come from the images' norms of the rounded rows: |x| <= (|x~| + 2^-25 sqrt(C)) / (1 - u), so
+//   s <= 1.001 (|q~| + max |k~|) + 2^-24 sqrt(C).
+// Rows outside fp16's domain (NaN in the image's first norm slot; fp32 has a value for them): see refine_threshold_f16_kernel.
 #include "global_match_common.h"
 
 namespace {
@@ -68,6 +89,78 @@ __global__ void refine_threshold_kernel(const unsigned *__restrict__ keys, const
     keys2[i] = k2;
     thr[i] = key_of(t);  // as an order-preserving key: the filter pass's workgroups tighten it by atomicMin
     slack[i] = sl;       // ... to (smallest bf16 distance they met) + slack: E only shrinks with U
+}
+
+// MANET_COMPUTE_F16_REFINE's form of the kernel above: one thread per QUERY (it reads its row of the fp16 image once: the scaled
+// norm pieces, the subnormal count, NaN and infinity elements), a loop over the objects.  256 threads = eight 32-query blocks, a
+// half-wave per block, so the block's counter is written ONCE, by its first lane, with the "incomplete" mark (bit 31: the
+// rescue pass -- the exact fp32 kernel -- takes the block's 256-query tile) already in it when the filter may not speak for the
+// block: a query of it lies outside fp16's domain (finite with a norm slot of NaN, or an infinity: fp32 has distances for it), or a
+// bank row does (META_F16_OOD: every block, the filter pass returns at once).  Distances of such rows are NaN in fp16: the
+// pre-pass's U of their pairs is NaN and their thresholds admit nothing, which no longer matters.  A NaN QUERY element settles
+// the pixel as in bf16r (every distance of the row is NaN in fp32 too).
+__global__ __launch_bounds__(256) void refine_threshold_f16_kernel(const unsigned *__restrict__ keys, const char *__restrict__ qimg,
+                                                                   long qblk_bytes, int units, int C, const int *__restrict__ meta,
+                                                                   long N, long N_pad, int n_ids, unsigned *__restrict__ thr,
+                                                                   float *__restrict__ slack, unsigned *__restrict__ keys2,
+                                                                   unsigned long long *__restrict__ stats,
+                                                                   unsigned *__restrict__ bcnt)
+{
+    const long n = (long)blockIdx.x * blockDim.x + threadIdx.x;  // (the grid covers N_pad exactly: a multiple of 512)
+    if (n == 0) stats[0] = stats[1] = 0ull;
+    const long nb = N_pad / QB;
+    if (n >= nb && n <= 2 * nb) bcnt[n] = 0u;  // (dense entries appended, number of tiles to rescue; nb < 2 nb + 1 <= N_pad)
+    const char *row = qimg + (n >> 5) * qblk_bytes + (n & 31) * 16;  // unit u of this query: row + u * QB * 16
+    auto elem = [&](int k) {
+        const int u = 2 * (k >> 4) + ((k >> 3) & 1);
+        return (unsigned)*(const unsigned short *)(row + (long)u * QB * 16 + (k & 7) * 2);
+    };
+    int sub = 0;
+    bool has_nan = false, has_inf = false;
+    for (int u = 0; u < units; ++u) {
+        const uint4 v = *(const uint4 *)(row + (long)u * QB * 16);
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+        const int k0 = 16 * (u >> 1) + 8 * (u & 1);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const unsigned b = (w[e >> 1] >> (16 * (e & 1))) & 0x7fffu;  // |-2 q~|
+            const bool in = k0 + e < C;
+            sub += (in && b != 0u && b < 0x0800u) ? 1 : 0;  // q~ nonzero and below 2^-14
+            has_nan = has_nan || (in && b > 0x7c00u);
+            has_inf = has_inf || (in && b == 0x7c00u);
+        }
+    }
+    const unsigned p0 = elem(C + 3);
+    const bool slot_nan = (p0 & 0x7fffu) > 0x7c00u;
+    const float qn2 = h2f(p0) + h2f(elem(C + 4)) * (1.0f / 2048.0f) + h2f(elem(C + 5)) * (1.0f / 16384.0f);
+    const bool bank_ood = meta[META_F16_OOD] != 0;
+    const bool exact = n < N && (bank_ood || (!has_nan && (has_inf || slot_nan)));
+    const bool mark = (__ballot(exact) >> (threadIdx.x & 32) & 0xffffffffull) != 0ull;  // this 32-query block's lanes
+    if ((n & 31) == 0) bcnt[n >> 5] = mark ? 0x80000000u : 0u;
+    const float u = 4.8828125e-4f;  // 2^-11
+    const float tiny = 6.1035156e-5f * (sqrtf((float)sub) + sqrtf((float)meta[META_F16_SUBN])) + 5.9604645e-8f * sqrtf((float)C);
+    const float kn = sqrtf(__uint_as_float((unsigned)meta[META_F16_KMAX]));
+    const float s = 1.001f * (sqrtf(fmaxf(qn2, 0.0f)) + kn) + 5.9604645e-8f * sqrtf((float)C), s2 = s * s;
+    const float eps = u * s + tiny;
+    const float a = 8.0f * (float)(C + 8) * 5.9604645e-8f * s2;
+    const float fix = 2.0f * eps * eps + 7.4505806e-9f + a;  // 2 eps^2 + 2^-27 + a
+    const float E0 = 2.0f * s * eps + fix;
+    for (int o = 0; o < n_ids; ++o) {
+        const long i = (long)o * N_pad + n;
+        unsigned k2 = 0xffffffffu;  // "no row": the exact distances meet here by atomicMin
+        const unsigned k = keys[i];
+        float t = -INFINITY, sl = 0.0f;  // no row of this object anywhere: no candidates, the result is the padding distance
+        if (k != 0xffffffffu && n < N) {
+            const float U = float_of(k);
+            if (has_nan || meta[META_NAN + o]) k2 = 0u;  // (as in refine_threshold_kernel)
+            const float E = 2.0f * eps * sqrtf(fmaxf(U, 0.0f) + E0 + a) + fix;
+            sl = 2.1f * E;
+            t = exact ? -INFINITY : U + sl;  // (NaN stays NaN: no candidates)
+        }
+        keys2[i] = k2;
+        thr[i] = key_of(t);
+        slack[i] = sl;
+    }
 }
 
 // MANET_EPI_REFINE_EXACT: no filter at all -- every 32-query block is marked incomplete, so the re-rank launch only writes the
@@ -285,9 +378,9 @@ __global__ __launch_bounds__(256) void refine_rerank_kernel(const SRC *__restric
 
 // MANET_COMPUTE_BF16_REFINE on a prepared bank (see the header comment).  `qimg` = the query's bf16 operand
 // image (made by the caller of this function), `qraw` = the same query as stored (fp32 / bf16, element strides).
-int run_refine(const char *qimg, const void *qraw, int q_dtype, long q_sn, long q_sc, const char *bws, const BankLayout &BL,
-               char *mws, const MatchLayout &ML, long N, int64_t M0, int C, int n_ids, float *out, float *mem, int flags,
-               hipStream_t st)
+int run_refine(int compute, const char *qimg, const void *qraw, int q_dtype, long q_sn, long q_sc, const char *bws,
+               const BankLayout &BL, char *mws, const MatchLayout &ML, long N, int64_t M0, int C, int n_ids, float *out, float *mem,
+               int flags, hipStream_t st)
 {
     const int *meta = (const int *)(bws + BL.off_meta), *sub_meta = (const int *)(bws + BL.off_sub_meta);
     unsigned *keys = (unsigned *)(mws + ML.off_keys), *keys2 = (unsigned *)(mws + ML.off_keys2);
@@ -300,7 +393,7 @@ int run_refine(const char *qimg, const void *qraw, int q_dtype, long q_sn, long 
     flags &= ~MANET_EPI_REFINE_EXACT;
     const long pairs = (long)n_ids * ML.N_pad;
     const MatchTune tune = match_tune();
-    auto plan = [&](int form) { return match_plan(N, M0, C, n_ids, 1, MANET_COMPUTE_BF16_REFINE, form, tune); };
+    auto plan = [&](int form) { return match_plan(N, M0, C, n_ids, 1, compute, form, tune); };
     MatchArgs A = {qimg, bws + BL.off_sub_pack, sub_meta, n_ids, ML.N_pad, keys, nullptr, thr, slack, stats, list, ML.bucket_cap, bcnt};
     if (force_exact) {
         hipLaunchKernelGGL(refine_force_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, ML.N_pad, n_ids, keys2, stats,
@@ -309,8 +402,12 @@ int run_refine(const char *qimg, const void *qraw, int q_dtype, long q_sn, long 
         // 1. pre-pass over the sub-sampled bank -> keys = U
         launch_match(plan(MATCH_FORM_REFINE_PRE), A, st);
         // 2. thresholds; exact keys and counters reset
-        hipLaunchKernelGGL(refine_threshold_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, (const unsigned *)keys,
-                           qimg, (long)ML.qblk_bytes, C, meta, N, ML.N_pad, n_ids, thr, slack, keys2, stats, bcnt);
+        if (compute == MANET_COMPUTE_F16_REFINE)
+            hipLaunchKernelGGL(refine_threshold_f16_kernel, dim3((unsigned)(ML.N_pad / 256)), dim3(256), 0, st, (const unsigned *)keys,
+                               qimg, (long)ML.qblk_bytes, ML.G.units, C, meta, N, ML.N_pad, n_ids, thr, slack, keys2, stats, bcnt);
+        else
+            hipLaunchKernelGGL(refine_threshold_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, (const unsigned *)keys,
+                               qimg, (long)ML.qblk_bytes, C, meta, N, ML.N_pad, n_ids, thr, slack, keys2, stats, bcnt);
         // 3. filter pass over the whole bank -> candidate list
         A.bpack = bws + BL.off_pack;
         A.meta = meta;
@@ -341,7 +438,7 @@ int run_refine(const char *qimg, const void *qraw, int q_dtype, long q_sn, long 
     launch_match(plan(force_exact ? MATCH_FORM_REFINE_RESCUE_EXACT : MATCH_FORM_REFINE_RESCUE), A, st);
     if (force_exact) manet_profile_record(st, false, 0);
     launch_global_finish(keys2, N, ML.N_pad, n_ids, flags & ~MANET_EPI_KEYS_ARMED, out, mem, N * n_ids, st);
-    return manet_check_launch("manet_global_match (bf16 filter + fp32 re-rank)");
+    return manet_check_launch("manet_global_match (filter + fp32 re-rank)");
 }
 
 // what both statistics readers share: checks, the layout, and blocking copies of the last filter pass's two counters
@@ -372,7 +469,8 @@ int manet_global_match_refine(const void *query, int emb_dtype, int64_t q_stride
                               float *out, float *mem_inout, int epilogue_flags, void *match_ws, size_t match_ws_bytes,
                               manet_stream_t stream)
 {
-    const int compute = MANET_COMPUTE_BF16_REFINE;
+    const int compute = (epilogue_flags & MANET_EPI_REFINE_F16) ? MANET_COMPUTE_F16_REFINE : MANET_COMPUTE_BF16_REFINE;
+    epilogue_flags &= ~MANET_EPI_REFINE_F16;
     int rc = check_common(N, M0, C, n_ids, 1, compute);
     if (rc) return rc;
     if (!query || !bank_ws || !out || !match_ws) return manet_set_error(MANET_E_INVALID, "null pointer");
@@ -387,7 +485,7 @@ int manet_global_match_refine(const void *query, int emb_dtype, int64_t q_stride
         return manet_set_error(MANET_E_WORKSPACE, "match workspace %zu < %zu bytes", match_ws_bytes, ML.total);
     hipStream_t st = (hipStream_t)stream;
     fill32((char *)match_ws + ML.off_keys, 0xffffffffu, (size_t)n_ids * ML.N_pad, st);
-    return run_refine((const char *)query_image, query, emb_dtype, (long)q_stride_n, (long)q_stride_c, (const char *)bank_ws, BL,
+    return run_refine(compute, (const char *)query_image, query, emb_dtype, (long)q_stride_n, (long)q_stride_c, (const char *)bank_ws, BL,
                       (char *)match_ws, ML, (long)N, M0, C, n_ids, out, mem_inout, epilogue_flags & ~MANET_EPI_KEYS_ARMED, st);
 }
 

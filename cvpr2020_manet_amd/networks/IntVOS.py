@@ -160,7 +160,7 @@ def _train_fused_ok(head, x):
 
 
 # arithmetic of the QK^T contraction used by the MODULE-LEVEL functions: "f32" (exact fp32 MFMA) | "bf16" | "bf16x3" |
-# "bf16r" | "f16".  An IntVOS instance carries its own (constructor argument / cfg.MODEL_MATCH_COMPUTE).
+# "bf16r" | "f16" | "f16r".  An IntVOS instance carries its own (constructor argument / cfg.MODEL_MATCH_COMPUTE).
 COMPUTE = "f32"
 
 # backward of the matching functions when they are differentiated, for the MODULE-LEVEL functions: "atomic" (float atomicAdd
@@ -639,7 +639,7 @@ class IntVOS(nn.Module):
         """cfg, feature_extracter: as the reference.  The rest is optional and this implementation's only (default: the
         cfg's MODEL_MATCH_COMPUTE / MODEL_EMB_DTYPE / MODEL_HEAD_POINTWISE / MODEL_CACHE_FRAMES when it has them, else
         "f32" / "f32" / "f32" / True):
-          compute       arithmetic of the global match: "f32" exact | "bf16" | "bf16x3" | "bf16r" | "f16" (fp16 MFMA)
+          compute       arithmetic of the global match: "f32" exact | "bf16" | "bf16x3" | "bf16r" | "f16" (fp16 MFMA) | "f16r" (fp16 filter + exact fp32 re-rank: the "f32" bits)
           emb_dtype     storage type of extract_feature's output: "f32" | "bf16" (the matching kernels then read 2-byte
                         embeddings end to end; the heads widen them)
           pointwise     the heads' 256-channel 1x1 layers in inference: "f32" exact fp32-MFMA kernel | "split" split-bf16

@@ -15,13 +15,19 @@ from . import _lib
 # "bf16r": bf16 filter + exact fp32 re-rank (MANET_COMPUTE_BF16_REFINE): MANET_COMPUTE_F32's result bit for bit, ~1.4x bf16's cost
 # "f16": fp16 MFMA on embeddings rounded to fp16 (MANET_COMPUTE_F16): bf16's cost, an input-rounding error 8x smaller; values with
 # |row|^2 > 65504 are outside its domain and give NaN (include/manet_hip.h)
+# "f16r": fp16 filter + exact fp32 re-rank (MANET_COMPUTE_F16_REFINE): bf16r with the filter in fp16 -- MANET_COMPUTE_F32's result bit for
+# bit on every input (rows outside fp16's domain go through the exact fp32 kernel), a threshold 8x tighter than bf16's
 COMPUTE = {"f32": _lib.COMPUTE_F32, "fp32": _lib.COMPUTE_F32, "bf16": _lib.COMPUTE_BF16,
-           "bf16x3": _lib.COMPUTE_BF16X3, "bf16r": _lib.COMPUTE_BF16_REFINE, "f16": _lib.COMPUTE_F16, "fp16": _lib.COMPUTE_F16}
+           "bf16x3": _lib.COMPUTE_BF16X3, "bf16r": _lib.COMPUTE_BF16_REFINE, "f16": _lib.COMPUTE_F16, "fp16": _lib.COMPUTE_F16,
+           "f16r": _lib.COMPUTE_F16_REFINE}
+_REFINE_NAME = {_lib.COMPUTE_BF16_REFINE: "bf16r", _lib.COMPUTE_F16_REFINE: "f16r"}
 
 
 def _image_kind(compute_code):
-    """operand images depend on the arithmetic only through this: bf16r packs exactly as bf16; f16 is a kind of its own (the
-    bf16 image's layout and size with fp16 elements: nothing but this comparison tells the two apart)"""
+    """operand images depend on the arithmetic only through this: bf16r packs exactly as bf16, f16r exactly as f16; f16 is a kind
+    of its own (the bf16 image's layout and size with fp16 elements: nothing but this comparison tells the two apart)"""
+    if compute_code == _lib.COMPUTE_F16_REFINE:
+        return _lib.COMPUTE_F16
     return _lib.COMPUTE_BF16 if compute_code == _lib.COMPUTE_BF16_REFINE else compute_code
 
 _ws_cache = {}
@@ -255,7 +261,7 @@ class PreparedBank:
             _lib.call("manet_bank_prepare_ex", ref.data_ptr(), _emb_code(ref), *_bank_strides(ref), lab.data_ptr(), M0, C, n_ids,
                       self.compute, self.ws.data_ptr(), self.ws.numel(), _stream_ptr(self.device))
 
-    # compute="bf16r", adaptive policy: a frame whose filter pass sent more than this share of its query tiles to the rescue
+    # compute="bf16r" / "f16r", adaptive policy: a frame whose filter pass sent more than this share of its query tiles to the rescue
     # pass (the exact fp32 kernel) cost the filter AND most of the fp32 kernel; the next ADAPT_FRAMES frames then skip the
     # filter (MANET_EPI_REFINE_EXACT: the same bits at the fp32 path's cost), after which one frame probes the filter again.
     # (The rescue launch is dealt to the rescued tiles only: a share r costs ~r of the fp32 kernel, so filtering pays below
@@ -265,7 +271,7 @@ class PreparedBank:
     def match(self, query_embeddings, k_nearest_neighbors=1, normalize=False, mem=None, out=None, adaptive=True):
         """query_embeddings: [..., C] float32 / bfloat16 tensor, or a PackedQuery (operand image made once,
         e.g. for every frame of a clip right after extract_feature: no per-frame pack pass).
-        adaptive (compute="bf16r" only): let the previous frames' rescue share decide whether this frame runs the bf16 filter at
+        adaptive (compute="bf16r" / "f16r" only): let the previous frames' rescue share decide whether this frame runs the filter at
         all (see ADAPT_SHARE); the result is the fp32 kernel's bit for bit either way.  The share arrives by an asynchronous copy
         and is read a frame late -- no synchronisation; nothing adapts inside a HIP-graph capture."""
         armed, raw = False, None
@@ -276,10 +282,11 @@ class PreparedBank:
                                  % (pq.C, pq.compute, self.C, self.compute))
             _refuse_autograd("PreparedBank.match", mem)
             qry, N, C, q_code, q_s0, q_s1 = pq.image, pq.N, pq.C, _lib.EMB_PACKED, 0, 0
-            armed = k_nearest_neighbors == 1 and self.compute != _lib.COMPUTE_BF16_REFINE
-            if self.compute == _lib.COMPUTE_BF16_REFINE:  # the exact re-rank reads the query as stored
+            armed = k_nearest_neighbors == 1 and self.compute not in _lib.REFINE_MODES
+            if self.compute in _lib.REFINE_MODES:  # the exact re-rank reads the query as stored
                 if pq.raw is None:
-                    raise ValueError("compute='bf16r' needs the embedding the operand image was made from (still alive)")
+                    raise ValueError("compute=%r needs the embedding the operand image was made from (still alive)"
+                                     % _REFINE_NAME[self.compute])
                 raw, _, _ = _flat(pq.raw, "query_embeddings")
         else:
             _refuse_autograd("PreparedBank.match", query_embeddings, mem)
@@ -297,7 +304,7 @@ class PreparedBank:
         mem_ptr = _mem_ptr(mem, N * self.n_ids)
         flags = (_lib.EPI_NORMALIZE if normalize else 0) | (_lib.EPI_KEYS_ARMED if armed else 0)
         self._last = (ws, N)  # (refine_stats)
-        refine = self.compute == _lib.COMPUTE_BF16_REFINE
+        refine = self.compute in _lib.REFINE_MODES
         adapt = refine and adaptive and not torch.cuda.is_current_stream_capturing()
         forced = False
         if adapt:
@@ -317,8 +324,9 @@ class PreparedBank:
         try:
             with _on(dev):
                 if raw is not None:
+                    mode = _lib.EPI_REFINE_F16 if self.compute == _lib.COMPUTE_F16_REFINE else 0
                     _lib.call("manet_global_match_refine", raw.data_ptr(), _emb_code(raw), *raw.stride(), qry.data_ptr(),
-                              self.ws.data_ptr(), N, self.M0, C, self.n_ids, out.data_ptr(), mem_ptr, flags, ws.data_ptr(),
+                              self.ws.data_ptr(), N, self.M0, C, self.n_ids, out.data_ptr(), mem_ptr, flags | mode, ws.data_ptr(),
                               ws.numel(), _stream_ptr(dev))
                 else:
                     _lib.call("manet_global_match_prepared_ex", qry.data_ptr(), q_code, q_s0, q_s1, self.ws.data_ptr(), N, self.M0,
@@ -344,21 +352,21 @@ class PreparedBank:
         return out
 
     def refine_stats(self):
-        """compute='bf16r': (candidate rows the filter pass appended, 1 if the candidate list overflowed and every pair
+        """compute='bf16r' / 'f16r': (candidate rows the filter pass appended, 1 if the candidate list overflowed and every pair
         scanned its object's rows instead) of the LAST match() on this bank; synchronises."""
-        if self.compute != _lib.COMPUTE_BF16_REFINE or getattr(self, "_last", None) is None:
-            raise RuntimeError("refine_stats: no compute='bf16r' match has run on this bank")
+        if self.compute not in _lib.REFINE_MODES or getattr(self, "_last", None) is None:
+            raise RuntimeError("refine_stats: no compute='bf16r' / 'f16r' match has run on this bank")
         ws, N = self._last
         torch.cuda.current_stream(ws.device).synchronize()  # (the C call copies on the null stream, which torch's side streams do not block)
         return _lib.query("manet_global_match_refine_stats", ws.data_ptr(), N, self.C, self.n_ids, out=(ctypes.c_int64,) * 2)
 
     def refine_stats_full(self):
-        """compute='bf16r', the LAST match() on this bank (synchronises): dict with the candidate rows the filter pass
+        """compute='bf16r' / 'f16r', the LAST match() on this bank (synchronises): dict with the candidate rows the filter pass
         listed, the overflow flag, and how many of the frame's 256-query tiles went through the rescue pass (the exact fp32
         kernel) -- `rescued_tile_fraction` is the distribution-dependent part of this mode's cost.  (The figures live in the
-        stream-shared match workspace: read them before another bf16r match runs on this stream.)"""
-        if self.compute != _lib.COMPUTE_BF16_REFINE or getattr(self, "_last", None) is None:
-            raise RuntimeError("refine_stats: no compute='bf16r' match has run on this bank")
+        stream-shared match workspace: read them before another such match runs on this stream.)"""
+        if self.compute not in _lib.REFINE_MODES or getattr(self, "_last", None) is None:
+            raise RuntimeError("refine_stats: no compute='bf16r' / 'f16r' match has run on this bank")
         ws, N = self._last
         torch.cuda.current_stream(ws.device).synchronize()  # (as refine_stats)
         s4 = (ctypes.c_int64 * 4)()
@@ -382,7 +390,7 @@ class PackedQuery:
             _lib.call("manet_query_pack", qry.data_ptr(), _emb_code(qry), *qry.stride(), N, C, self.compute,
                       self.image.data_ptr(), self.image.numel(), _stream_ptr(qry.device))
         self.device = qry.device
-        self.raw = query_embeddings  # (compute="bf16r": the exact re-rank reads the embedding itself)
+        self.raw = query_embeddings  # (compute="bf16r" / "f16r": the exact re-rank reads the embedding itself)
 
 
 class PreparedFrame:
@@ -393,7 +401,7 @@ class PreparedFrame:
 
     def __init__(self, ws, h, w, C, compute, max_distance, keep=None, raw=None):
         self.ws, self.h, self.w, self.C, self.compute, self.max_distance = ws, h, w, C, compute, max_distance
-        self.raw = raw  # the [C, h, w] embedding as an [h, w, C] view (compute="bf16r" re-ranks from it)
+        self.raw = raw  # the [C, h, w] embedding as an [h, w, C] view (compute="bf16r" / "f16r" re-rank from it)
         self.N = h * w
         self.image = ws  # the operand image sits at the start of the frame workspace (a MANET_EMB_PACKED query)
         self.device = ws.device

@@ -739,7 +739,8 @@ def parse_args(argv=None):
                     help="the heads' 1x1 convolutions: exact fp32-MFMA kernel (default), the split-bf16 MFMA kernel, or the "
                          "framework's GEMM")
     ap.add_argument("--compute", type=str, default=None, help="arithmetic of the global match (f32 | bf16 | bf16x3 | bf16r | f16: fp16 MFMA on embeddings rounded to fp16, "
-                    "bf16's cost at an 8x smaller rounding error; values with |row|^2 > 65504 give NaN)")
+                    "bf16's cost at an 8x smaller rounding error; values with |row|^2 > 65504 give NaN | f16r: fp16 filter + exact "
+                    "fp32 re-rank, the f32 result bit for bit)")
     ap.add_argument("--emb-dtype", type=str, default=None, help="storage of the embeddings (f32 | bf16)")
     ap.add_argument("--prepare-clip", action="store_true",
                     help="prepare every frame's operands up front (model.prepare_clip) instead of on first use")

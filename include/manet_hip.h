@@ -93,6 +93,18 @@ typedef void *manet_stream_t; /* a hipStream_t */
  * row propagates, here and in the other modes.  Elements below 2^-14 in magnitude are fp16 subnormals; whether the matrix pipe
  * keeps or flushes them is the hardware's choice (each such element changes a distance by at most 2 |q~_c| |k~_c|). */
 #define MANET_COMPUTE_F16 4
+/* fp16 filter + exact fp32 re-rank (k_nn = 1, C <= 106; opt-in, inference only): MANET_COMPUTE_BF16_REFINE with the filter and
+ * the pre-pass in fp16 arithmetic on MANET_COMPUTE_F16's operand images.  The filter's threshold is linear in the filter
+ * arithmetic's unit roundoff, 2^-11 here against bf16's 2^-8, so it keeps several times fewer candidate rows on embeddings whose
+ * neighbours lie close together.  The result EQUALS MANET_COMPUTE_F32's bit for bit on EVERY input; workspace sizes, launch plans,
+ * statistics (manet_global_match_refine_stats*) and MANET_EPI_REFINE_EXACT are MANET_COMPUTE_BF16_REFINE's.
+ * Rows outside fp16's domain (see MANET_COMPUTE_F16: |row|^2 of the rounded values > 65504, or an infinity) have no finite fp16
+ * distance, so the filter cannot speak for them; the fp32 kernel can.  A QUERY row outside the domain sends its own 256-query
+ * tile through the exact fp32 kernel (the rescue pass).  A BANK row outside the domain concerns every query, and the rescue
+ * pass is per query tile: the filter pass then returns at once and every tile is rescued -- such a frame costs the fp32 path's
+ * time plus the pre-pass (1/8 to 1/16 of an fp16 pass).  NaN rows propagate as in MANET_COMPUTE_BF16_REFINE.  Elements that are
+ * fp16 subnormals are counted per row and paid for in the threshold, whether the matrix pipe keeps or flushes them. */
+#define MANET_COMPUTE_F16_REFINE 6 /* (5 stays unassigned: tests/test_f16_match_abi.py keeps it as THE code no build accepts) */
 
 /* storage type of an embedding operand of the *_ex entry points (take the producer's layout) */
 #define MANET_EMB_F32 0    /* float */
@@ -105,11 +117,14 @@ typedef void *manet_stream_t; /* a hipStream_t */
  * holds 0xff bytes throughout (e.g. it filled it once and has only used it for calls with this flag since); the call
  * then skips its fill launch and leaves the workspace in that state again (the epilogue re-arms what it reads). */
 #define MANET_EPI_KEYS_ARMED 2
-/* MANET_COMPUTE_BF16_REFINE only: skip the bf16 filter and let the rescue pass (the exact fp32 kernel) take every query tile --
+/* MANET_COMPUTE_BF16_REFINE / _F16_REFINE only: skip the filter and let the rescue pass (the exact fp32 kernel) take every query tile --
  * the same bits at the fp32 path's cost (+ ~0.03 ms), for a caller that knows from the previous frame
  * (manet_global_match_refine_rescued_async) that the bf16 pass cannot tell these embeddings apart; without it such a frame costs
  * the filter pass AND the fp32 kernel. */
 #define MANET_EPI_REFINE_EXACT 4
+/* manet_global_match_refine only (it has no `compute` argument): the bank workspace and the query image are
+ * MANET_COMPUTE_F16_REFINE's (fp16 images), not MANET_COMPUTE_BF16_REFINE's. */
+#define MANET_EPI_REFINE_F16 8
 
 const char *manet_version(void);
 const char *manet_last_error_string(void);
@@ -219,6 +234,8 @@ int manet_embed_finish(const float *conv_out, int64_t s_f, int64_t s_y, int64_t 
 /* MANET_COMPUTE_BF16_REFINE on a prepared bank when the query's packed image exists already (manet_frame_prepare /
  * manet_query_pack with MANET_COMPUTE_BF16 or _BF16_REFINE): the fp32 re-rank also needs the query as stored, so this entry
  * point takes both.  query_image == NULL: same as manet_global_match_prepared_ex(..., MANET_COMPUTE_BF16_REFINE, ...).
+ * With MANET_EPI_REFINE_F16 in epilogue_flags the call is MANET_COMPUTE_F16_REFINE's: the bank prepared for that mode, the image
+ * made with MANET_COMPUTE_F16 or _F16_REFINE.  The statistics calls below serve both modes (one workspace layout).
  * manet_global_match_refine_stats reads back (blocking copy on the NULL stream -- tests / benchmarks; it does not wait for work on
  * non-blocking streams: synchronise the stream the match ran on first, as ops.PreparedBank.refine_stats does) what the last call on `match_ws` did:
  * candidate rows the filter pass listed (+, per 32 x 32 block it listed whole, the number of (query, half pass) lanes that held

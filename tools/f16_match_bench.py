@@ -8,7 +8,15 @@
   e2e      examples/propagate_clip.py's propagated frame (--fused-mask-step, roi bank) with the same clip under f32, f16 and
            bf16: frames/s, max logit error and the share of mask pixels that differ from the f32 run.
 
-python3 tools/f16_match_bench.py [--out FILE.json] [--rounds 7] [--launches 40] [--skip-e2e] [--modes bf16,f16]"""
+  --refine compute="f16r" (fp16 filter + exact fp32 re-rank) against "bf16r" and "f32", the same method: per data set the three
+           modes alternate in one process on the SAME tensors, a round = `launches` whole matches between two device events (a
+           refine match is several launches), per mode the median and the spread of the round medians; with the candidate rows
+           per pair and the rescued-tile share of both refine modes (adaptive policy off).  Shapes: cfg3 (120x214 grid, 5-frame
+           bank, 4 ids) and the example's roi bank (one annotated frame labelled by rough_ROI, 3 ids) x data: i.i.d.,
+           bench.py's video-like and smooth clips, the example encoder's embeddings.  Then the example's propagated frame
+           (--fused-mask-step, roi bank) under f32 | bf16r | f16r: frames/s, masks compared with the f32 run's.
+
+python3 tools/f16_match_bench.py [--out FILE.json] [--rounds 7] [--launches 40] [--skip-e2e] [--modes bf16,f16] [--refine]"""
 import argparse
 import ctypes
 import json
@@ -94,6 +102,92 @@ def e2e_part(rounds):
     return out
 
 
+REFINE_MODES = ("f32", "bf16r", "f16r")
+
+
+def _refine_data(dev):
+    """{(shape, data): (bank rows [M, C], int32 labels [M], query [h, w, C] view, n_ids)}"""
+    import bench
+    import propagate_clip as pc
+    h, w, T, n_ids = CFG["cfg3"]
+    out = {}
+    args = pc.parse_args(["--fused-mask-step"])
+    cfg, model = pc.build_model(dev)
+    enc = pc.synthetic_clip(model, dev, T + 1, args.height, args.width, args.objects).float().contiguous()  # [T + 1, C, 120, 214]
+    assert tuple(enc.shape[2:]) == (h, w), enc.shape
+    g = torch.Generator(device=dev).manual_seed(20200614)
+    clips = {"iid": (torch.relu(torch.randn(T + 1, 100, h, w, generator=g, device=dev)) * 0.1,
+                     torch.randint(0, n_ids, (T + 1, h, w), generator=g, device=dev, dtype=torch.int32)),
+             "video": bench._synthetic_scene("video", T + 1, h, w, n_ids, 0.1, dev, 20200617),
+             "smooth": None,
+             "encoder": (enc, torch.randint(0, n_ids, (T + 1, h, w), generator=g, device=dev, dtype=torch.int32))}
+    roi = pc.rough_ROI(pc.make_scribble(dev, h, w, args.objects)).reshape(-1).to(torch.int32)  # -1 = unlabelled, ids 0..objects
+    for data in ("iid", "video", "smooth", "encoder"):
+        emb, lab = clips[data] if clips[data] is not None else bench._synthetic_scene("smooth", T + 1, h, w, n_ids, 0.1, dev, 20200617)
+        C = emb.shape[1]
+        rows = lambda f: emb[f].permute(1, 2, 0).reshape(-1, C)  # noqa: E731
+        q = emb[T // 2 + 1].permute(1, 2, 0)  # a frame from the middle of the clip; the bank: the other T
+        bank = [f for f in range(T + 1) if f != T // 2 + 1]
+        out[("cfg3", data)] = (torch.cat([rows(f) for f in bank]).contiguous(), torch.cat([lab[f].reshape(-1) for f in bank]).contiguous(),
+                               q, n_ids)
+        out[("roi", data)] = (rows(T // 2).contiguous(), roi, q, args.objects + 1)
+    return out
+
+
+def refine_part(rounds, launches):
+    dev = torch.device("cuda:0")
+    out = {}
+    for (shape, data), (k, lab, q, n_ids) in _refine_data(dev).items():
+        banks = {m: ops.PreparedBank(k, lab, n_ids, compute=m) for m in REFINE_MODES}
+        want = banks["f32"].match(q)
+        res = {"bank_rows": int((lab >= 0).sum()), "queries": q.shape[0] * q.shape[1], "n_ids": n_ids, "C": k.shape[1]}
+        for m in REFINE_MODES[1:]:
+            assert torch.equal(banks[m].match(q, adaptive=False), want), (shape, data, m)
+            st = banks[m].refine_stats_full()
+            res[m] = {"candidate_rows_per_pair": round(st["candidate_rows_per_pair"], 2),
+                      "rescued_tile_fraction": round(st["rescued_tile_fraction"], 4), "list_overflowed": st["list_overflowed"]}
+        res["f32"] = {}
+
+        def timed(m):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(launches):
+                banks[m].match(q, normalize=True, adaptive=False)
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b) / launches
+
+        for m in REFINE_MODES:  # warm-up
+            timed(m)
+        med = {m: [] for m in REFINE_MODES}
+        for _ in range(rounds):
+            for m in REFINE_MODES:
+                med[m].append(timed(m))
+        for m in REFINE_MODES:
+            res[m].update({"round_ms": [round(x, 4) for x in med[m]], "median_ms": round(statistics.median(med[m]), 4),
+                           "spread_ms": round(max(med[m]) - min(med[m]), 4)})
+        out["%s/%s" % (shape, data)] = res
+        print(shape, data, json.dumps(res), flush=True)
+        del banks
+    return out
+
+
+def refine_e2e_part(rounds):
+    import propagate_clip as pc
+    dev = torch.device("cuda:0")
+    out, masks = {}, {}
+    for compute in REFINE_MODES:
+        args = pc.parse_args(["--fused-mask-step", "--compute", compute, "--bank", "roi", "--rounds", str(rounds)])
+        res, clip, final = pc.run_single(args, dev)
+        masks[compute] = final
+        out[compute] = {"frames_per_s": round(res["eager_frames_per_s"], 1), "ms_per_round": round(res["eager_ms_per_round"], 2),
+                        "bank_rows": res["bank_rows"], "grid": res["grid"], "mask_digest": res["mask_digest"],
+                        "masks_equal_f32": bool(torch.equal(final, masks["f32"]))}
+        print(compute, json.dumps(out[compute]), flush=True)
+        del clip
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", type=str, default=None)
@@ -102,13 +196,19 @@ def main():
     ap.add_argument("--e2e-rounds", type=int, default=3)
     ap.add_argument("--skip-e2e", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
+    ap.add_argument("--refine", action="store_true", help="the f16r / bf16r / f32 comparison instead of the f16 / bf16 one")
     ap.add_argument("--modes", type=str, default=",".join(MODES), help="modes of the kernel part (bf16 alone: a library without f16)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     res = {"device": torch.cuda.get_device_name(0)}
-    if not args.skip_kernel:
+    if args.refine:
+        if not args.skip_kernel:
+            res["match"] = refine_part(args.rounds, args.launches)
+        if not args.skip_e2e:
+            res["e2e"] = refine_e2e_part(args.e2e_rounds)
+    elif not args.skip_kernel:
         res["kernel"] = kernel_part(args.rounds, args.launches, tuple(args.modes.split(",")))
-    if not args.skip_e2e:
+    if not args.skip_e2e and not args.refine:
         res["e2e"] = e2e_part(args.e2e_rounds)
     line = json.dumps(res)
     print(line)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""GPU fuzz: compute="bf16r" against compute="f32" (bit for bit, NaN patterns included) on randomly STRUCTURED banks -- mixtures
+"""GPU fuzz: compute="bf16r" (or "f16r") against compute="f32" (bit for bit, NaN patterns included) on randomly STRUCTURED banks -- mixtures
 of i.i.d. rows, near-duplicates of a few base rows, smooth ramps, constant bands, unlabelled rows, empty objects -- over random
-sizes / channel counts / id counts / storage types.  usage: tools/fuzz_bf16r.py [cases] [seed]"""
+sizes / channel counts / id counts / storage types.  compute="f16r" adds the scales 30 and 40 to the mixture: |row|^2 then lies
+on both sides of fp16's domain edge (65504 at C = 100), bank rows and queries alike.
+usage: tools/fuzz_bf16r.py [cases] [seed] [bf16r | f16r]"""
 import os
 import sys
 
@@ -10,12 +12,15 @@ import torch  # noqa: E402
 from cvpr2020_manet_amd import ops  # noqa: E402
 
 
-def make_case(g, dev):
+SCALES = {"bf16r": [0.05, 0.1, 0.3, 1.0], "f16r": [0.05, 0.1, 0.3, 1.0, 30.0, 40.0]}
+
+
+def make_case(g, dev, scales=SCALES["bf16r"]):
     ri = lambda lo, hi: int(torch.randint(lo, hi + 1, (1,), generator=g).item())  # noqa: E731
     C = [4, 7, 16, 26, 30, 50, 64, 99, 100, 101, 106][ri(0, 10)]
     n_ids = ri(1, 6)
     N, M = ri(1, 2500), ri(1, 40000)
-    scale = [0.05, 0.1, 0.3, 1.0][ri(0, 3)]
+    scale = scales[ri(0, len(scales) - 1)]
     gd = torch.Generator(device=dev).manual_seed(ri(0, 2 ** 31 - 1))
     rn = lambda *s: torch.randn(*s, generator=gd, device=dev)  # noqa: E731
     kind = ri(0, 4)
@@ -65,14 +70,14 @@ def same(a, b):
     return bool(torch.equal(na, nb)) and bool(torch.equal(torch.where(na, torch.zeros_like(a), a), torch.where(nb, torch.zeros_like(b), b)))
 
 
-def run(cases, seed, verbose=True):
+def run(cases, seed, verbose=True, compute="bf16r"):
     dev = torch.device("cuda", 0)
     g = torch.Generator().manual_seed(seed)
     bad = 0
     for i in range(cases):
-        q, k, lab, n_ids, info = make_case(g, dev)
+        q, k, lab, n_ids, info = make_case(g, dev, SCALES[compute])
         want = ops.global_match(k, q, lab, n_ids, compute="f32")
-        bank = ops.PreparedBank(k, lab, n_ids, compute="bf16r")
+        bank = ops.PreparedBank(k, lab, n_ids, compute=compute)
         got = bank.match(q, adaptive=False)
         ok = same(got, want)
         st = bank.refine_stats_full()
@@ -86,6 +91,6 @@ def run(cases, seed, verbose=True):
 if __name__ == "__main__":
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     s = int(sys.argv[2]) if len(sys.argv) > 2 else 1
-    b = run(n, s, verbose=os.environ.get("VERBOSE") == "1")
+    b = run(n, s, verbose=os.environ.get("VERBOSE") == "1", compute=sys.argv[3] if len(sys.argv) > 3 else "bf16r")
     print("%d cases, %d mismatches" % (n, b))
     sys.exit(1 if b else 0)
