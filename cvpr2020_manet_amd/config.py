@@ -55,6 +55,7 @@ FLAGS = [
     #   MODEL_HEAD_MEMO_MB           cap of the heads' memoised layer-1 shared-half terms on the cached frames
     #   MODEL_LOCAL_VOLUME_DTYPE     storage of the stored local-match volumes: f32 | f16 (OPTIONAL_FLAGS below)
     #   MODEL_TRAIN_INPUTS           the heads' input in training: framework | fused (one HIP launch each way; OPTIONAL_FLAGS below)
+    #   MODEL_HEAD_ACT               activations between the stages of the propagation heads in inference: f32 | f16 (OPTIONAL_FLAGS below)
     ("MODEL_MATCH_COMPUTE", S, "f32"), ("MODEL_EMB_DTYPE", S, "f32"), ("MODEL_HEAD_POINTWISE", S, "f32"),
     ("MODEL_CACHE_FRAMES", B, True), ("MODEL_LOCAL_VOLUME_CACHE_MB", I, 8192), ("MODEL_LOCAL_VOLUME_LAZY", B, False),
     ("MODEL_HEAD_MEMO_MB", I, 8192),
@@ -72,8 +73,8 @@ FLAGS = [
 
 # (flag, type) -- accepted on the command line, but an attribute of the cfg only when given: the default cfg keeps exactly the
 # attributes it had (IntVOS reads these with getattr: absent = the default, "f32" for MODEL_LOCAL_VOLUME_DTYPE,
-# "framework" for MODEL_TRAIN_INPUTS)
-OPTIONAL_FLAGS = [("MODEL_LOCAL_VOLUME_DTYPE", S), ("MODEL_TRAIN_INPUTS", S)]
+# "framework" for MODEL_TRAIN_INPUTS, "f32" for MODEL_HEAD_ACT)
+OPTIONAL_FLAGS = [("MODEL_LOCAL_VOLUME_DTYPE", S), ("MODEL_TRAIN_INPUTS", S), ("MODEL_HEAD_ACT", S)]
 
 
 def build_parser():

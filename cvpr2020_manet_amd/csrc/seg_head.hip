@@ -24,6 +24,8 @@
 // Tap order (ky outer, kx inner, fmaf chain per output) is the r1 kernel's and the oracle's: bit-identical.
 #include "manet_common.h"
 
+#include <type_traits>
+
 namespace {
 
 constexpr int DW_K = 7, DW_R = 3;
@@ -51,12 +53,27 @@ constexpr int DW_TY = DwStd::TY, DW_TX = DwStd::TX, DW_IMG = DwStd::IMG;
 // (the 4-byte-load form of odd widths needs ~148 registers: three workgroups per CU -- at four it spilled 20 of them, r4)
 // RELU_IN / RELU (r5): compile-time -- as run-time flags each staged element paid a select on top of its max (76 v_cndmask +
 // 76 v_max per item against 392 packed FMAs), each output one more.  (Worth ~1 % on a warm GPU: the kernel hides it.)
-template <typename SH, bool FAST, bool RELU_IN, bool RELU>
-__device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *__restrict__ in, int C, int h, int w,
+// TI / TO (head_act="f16", dwconv7x7_bn_relu_f16_kernel): the element types of the input and output planes, float or _Float16.
+// Halves are widened while staging (a FAST load is then 4 bytes = two halves) and the output is rounded once, to nearest even,
+// after the fp32 epilogue: out = rn16(min(relu(.), 65504)) with a NaN kept; the LDS image and the arithmetic are fp32 either way.
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+constexpr float F16_MAX = 65504.0f;
+template <typename T> struct DwPair { typedef f32x2 type; };
+template <> struct DwPair<_Float16> { typedef f16x2 type; };
+// relu and the saturation of an fp16 store, both keeping a NaN (fmaxf / fminf return the other operand)
+__device__ __forceinline__ float f16_relu(float v) { return v <= 0.0f ? 0.0f : v; }
+__device__ __forceinline__ float f16_sat(float v) { return v > F16_MAX ? F16_MAX : v; }
+
+template <typename SH, bool FAST, bool RELU_IN, bool RELU, typename TI = float, typename TO = float>
+__device__ __forceinline__ void dw_tile(float *__restrict__ tile, const TI *__restrict__ in, int C, int h, int w,
                                         const float *__restrict__ weight, const float *__restrict__ bias,
-                                        const float *__restrict__ scale, const float *__restrict__ shift, float *__restrict__ out,
+                                        const float *__restrict__ scale, const float *__restrict__ shift, TO *__restrict__ out,
                                         int c, int b_first, int b_end, int x0, int y0)
 {
+    typedef typename DwPair<TI>::type ld_t;
+    constexpr unsigned IB = sizeof(TI), OB = sizeof(TO);
     constexpr bool relu_in = RELU_IN, relu = RELU;
     constexpr int DW_LW = SH::LW, DW_NP = SH::NP, DW_IMG = SH::IMG, DW_TY = SH::TY;
     const long plane = (long)h * w;
@@ -67,7 +84,7 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
     // pass 1: every load of the thread is issued (clamped addresses, no predicate anywhere near them); pass 2 selects,
     // rectifies and stores.  Written as one loop, hipcc sinks each load into the branch of its select and waits
     // vmcnt(0) there: 15 serial L2 round trips per thread (r2 trace: this, not the 392 FMAs, was the kernel's time).
-    f32x2 ld[KI][3];
+    ld_t ld[KI][3];
     unsigned off[KI][3];  // BYTE offsets inside a plane (the same for every batch item)
 #pragma unroll
     for (int k = 0; k < KI; ++k) {
@@ -77,7 +94,7 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
             const int yc = min(max(y0 - DW_R + 2 * p + e, 0), h - 1);
-            off[k][e] = 4u * (unsigned)(yc * w + min(max(xx, 0), FAST ? w - 2 : w - 1));
+            off[k][e] = IB * (unsigned)(yc * w + min(max(xx, 0), FAST ? w - 2 : w - 1));
         }
     }
     auto issue_loads = [&](int b) __attribute__((always_inline)) {
@@ -92,10 +109,10 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
                 if (FAST) {
-                    ld[k][e] = *(const f32x2 *)(src + off[k][e]);
+                    ld[k][e] = *(const ld_t *)(src + off[k][e]);
                 } else {
-                    ld[k][e][0] = *(const float *)(src + off[k][e]);
-                    ld[k][e][1] = *(const float *)(src + (unsigned)(off[k][e] - 4u * (unsigned)min(max(xx, 0), w - 1) + 4u * (unsigned)min(max(xx + 1, 0), w - 1)));
+                    ld[k][e][0] = *(const TI *)(src + off[k][e]);
+                    ld[k][e][1] = *(const TI *)(src + (unsigned)(off[k][e] - IB * (unsigned)min(max(xx, 0), w - 1) + IB * (unsigned)min(max(xx + 1, 0), w - 1)));
                 }
             }
         }
@@ -122,8 +139,8 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
             for (int e = 0; e < 3; ++e) {
                 const int yy = y0 - DW_R + 2 * p + e;
                 const bool yok = yy >= 0 && yy < h && iok;
-                rv[e][0] = (yok && xx >= 0 && xx < w) ? ld[k][e][0] : 0.0f;
-                rv[e][1] = (yok && xx + 1 >= 0 && xx + 1 < w) ? ld[k][e][1] : 0.0f;
+                rv[e][0] = (yok && xx >= 0 && xx < w) ? (float)ld[k][e][0] : 0.0f;
+                rv[e][1] = (yok && xx + 1 >= 0 && xx + 1 < w) ? (float)ld[k][e][1] : 0.0f;
                 if (relu_in) rv[e] = __builtin_elementwise_max(rv[e], f32x2{0.0f, 0.0f});
             }
             if (iok) {
@@ -182,12 +199,21 @@ __device__ __forceinline__ void dw_tile(float *__restrict__ tile, const float *_
             for (int e = 0; e < 4; ++e) {
                 const int y = y0 + 4 * t + e;
                 if (y >= h) continue;
-                float *dst = (float *)((char *)(out + ((long)b * C + c) * plane) + 4u * (unsigned)(y * w + x));
+                TO *dst = (TO *)((char *)(out + ((long)b * C + c) * plane) + OB * (unsigned)(y * w + x));
                 float r[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float o = fmaf((e < 2 ? accA[j][e] : accB[j][e - 2]) + bc, sc, sh);
-                    r[j] = relu ? fmaxf(o, 0.0f) : o;
+                    if constexpr (OB == 2) r[j] = f16_sat(relu ? f16_relu(o) : o);
+                    else r[j] = relu ? fmaxf(o, 0.0f) : o;
+                }
+                if constexpr (OB == 2) {
+                    // the thread's four columns leave as one 8-byte store (rows of halves are 4-byte aligned: w is even); the
+                    // plane's last column group holds four columns or two
+                    const f16x4 r16 = __builtin_convertvector((f32x4){r[0], r[1], r[2], r[3]}, f16x4);
+                    if (x + 3 < w) *(f16x4 *)dst = r16;
+                    else if (x + 1 < w) *(f16x2 *)dst = f16x2{r16[0], r16[1]};
+                    continue;
                 }
                 if (FAST && x + 3 < w) {  // w even, plane 8-byte aligned: float2 stores are always aligned
 #pragma unroll
@@ -237,6 +263,34 @@ __global__ __launch_bounds__(256, FAST ? 4 : 3) void dwconv7x7_bn_relu_kernel(co
     } else {
         dw_tile<DwNarrow, FAST, RELU_IN, RELU>(tile, in, C, h, w, weight, bias, scale, shift, out, c, b_first, b_end,
                                                (nstd / nty) * DwStd::TX, (tile_ - nstd) * DwNarrow::TY);
+    }
+}
+
+// head_act="f16": the same stage with its output -- and, behind layer 1, its input -- stored as fp16: the FAST (even w) form,
+// relu on, the same block map, batch walk and tiles; dw_tile's fp32 LDS image and fmaf chain, so the result is the fp32 kernel's,
+// saturated at 65504 and rounded once.
+template <bool IN16>
+__global__ __launch_bounds__(256, 4) void dwconv7x7_bn_relu_f16_kernel(const void *__restrict__ in, int B, int C, int h, int w,
+                                                                     const float *__restrict__ weight, const float *__restrict__ bias,
+                                                                     const float *__restrict__ scale, const float *__restrict__ shift,
+                                                                     _Float16 *__restrict__ out, int per_item, int ntx, int nty, int nstd,
+                                                                     int ntile_)
+{
+    typedef typename std::conditional<IN16, _Float16, float>::type TI;
+    const int xcd_ = blockIdx.x & 7, j_ = blockIdx.x >> 3;
+    const int tile_ = j_ % ntile_, bz = (j_ / ntile_) * 8 + xcd_;
+    if (bz >= (per_item ? B * C : C)) return;
+    __shared__ __attribute__((aligned(16))) float tile[2 * DW_IMG];
+    const int c = per_item ? bz % C : bz;
+    const int b_first = per_item ? bz / C : 0, b_end = per_item ? b_first + 1 : B;
+    if (tile_ < nstd) {
+        const int ncol = nstd / nty;
+        const int bx = tile_ % ncol, by = tile_ / ncol;
+        dw_tile<DwStd, true, false, true, TI, _Float16>(tile, (const TI *)in, C, h, w, weight, bias, scale, shift, out, c, b_first, b_end,
+                                                        bx * DwStd::TX, by * DwStd::TY);
+    } else {
+        dw_tile<DwNarrow, true, false, true, TI, _Float16>(tile, (const TI *)in, C, h, w, weight, bias, scale, shift, out, c, b_first,
+                                                           b_end, (nstd / nty) * DwStd::TX, (tile_ - nstd) * DwNarrow::TY);
     }
 }
 
@@ -694,6 +748,204 @@ __global__ __launch_bounds__(X3_NT, NP == 3 ? 2 : 3) void conv1x1_x3_kernel(cons
                 if (add) v += add[(long)co * HW + p];
                 if (relu_out) v = fmaxf(v, 0.0f);
                 dst[(long)co * HW + p] = v;
+            }
+    }
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The 1x1 stage of head_act="f16": fp16 activation in, fp16 activation (or the fused fp32 logits) out, the folded weight rounded
+// once to fp16: exact fp16 x fp16 products on v_mfma_f32_32x32x16_f16, fp32 accumulators, an fp32 epilogue (+ b2, + the fp32
+// `add` term, ReLU) and one rounding at the store: rn16(min(., 65504)), a NaN kept.  One MFMA per 32 x 32 x 16 block where the
+// split kernel spends three and a register-side split, and half the bytes each way.
+//   workgroup = 128 pixels x 256 output channels, 4 waves = (pixel half) x (channel half), 128 accumulators per lane;
+//   weights: packed once per fold (conv1x1_f16_pack_kernel) as the MFMA operand image [chunk][co block 8][lane 64] x 16 bytes
+//     (conv1x1_x3_pack_kernel's layout, one piece), 8 KiB per 16 input channels, LDS-DMA'd chunk by chunk;
+//   activation: rows [16 k][128 px] of halves arrive by 16-byte LDS-DMA (h*w a multiple of 8) and are read TRANSPOSED
+//     (ds_read_b64_tr_b16: two reads give a lane the 8 k of its pixel column).  The DMA's lanes choose WHICH 16 bytes they fetch,
+//     so the LDS image is laid out for those reads at no cost: chunk ch of row r sits at 256 r + 16 (ch ^ (((r & 3) << 2) |
+//     ((r >> 2) & 3))) -- plain 256-byte rows are 4-way conflicts for the transposed read.  Every lane holds a valid address at
+//     every read (EXEC is all ones in the loop: no early return, no lane-dependent branch in front of it);
+//   ring of 4 chunk slots, fetched three steps ahead; a step waits with a counted vmcnt (the younger chunks stay in flight) and
+//     meets the others at a raw s_barrier behind lgkmcnt(0) -- __syncthreads() would drain the DMA queue;
+//   operand order by form: HEAD (fused logits) -- weights as A, so a lane owns a pixel and its channels sit in its registers, as
+//     in conv1x1_x3_kernel; else the ACTIVATION as A -- a lane owns a channel and 4 consecutive pixels per register quad, which
+//     leave as one 8-byte store (no lane ever stores a single half), the fp32 term arrives as one 16-byte load.
+//   any Cin >= 1 (rows past Cin are clamped reads against zero weight rows); the plane's last tile computes clamped columns
+//   that are never stored.
+constexpr int H16_P = 128, H16_KC = 16, H16_NT = 256, H16_NB = 4, H16_WCHUNK = 8 * 1024, H16_XCHUNK = H16_KC * H16_P * 2;
+typedef short h16_s4 __attribute__((__vector_size__(8)));
+typedef __attribute__((address_space(3))) h16_s4 *h16_lds_ptr;
+
+// w2t [Cin][256] fp32 -> [chunk][co block 8][lane 64] x 16 bytes; lane l of block b holds output channel 32 b + (l & 31), input
+// channels 16 chunk + 8 (l >> 5) + 0..7, each rounded to nearest-even fp16 (zero past Cin)
+__global__ __launch_bounds__(256) void conv1x1_f16_pack_kernel(const float *__restrict__ w2t, int Cin, uint4 *__restrict__ wpk, int n_chunks)
+{
+    const int item = blockIdx.x * 256 + threadIdx.x;  // (chunk, block, lane)
+    if (item >= n_chunks * 8 * 64) return;
+    const int lane = item & 63, blk = (item >> 6) & 7, c = item >> 9;
+    const int co = 32 * blk + (lane & 31), k0 = 16 * c + 8 * (lane >> 5);
+    f16x8 v;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (_Float16)(k0 + j < Cin ? w2t[(long)(k0 + j) * PW_CO + co] : 0.0f);
+    wpk[item] = __builtin_bit_cast(uint4, v);
+}
+
+// OUT32: the result leaves as fp32, unrounded (layer 1's shared-half term, which joins the per-object half in ITS epilogue)
+template <bool HEAD, bool OUT32 = false>
+__global__ __launch_bounds__(H16_NT, 3) void conv1x1_f16_kernel(const _Float16 *__restrict__ in, long in_bs, int Cin, long HW,
+                                                               const char *__restrict__ wpk, const float *__restrict__ b2,
+                                                               const float *__restrict__ add, int relu_out,
+                                                               void *__restrict__ out, const float *__restrict__ head_w,
+                                                               const float *__restrict__ head_b, float *__restrict__ head_out)
+{
+    __shared__ __attribute__((aligned(1024))) char wbuf[H16_NB][H16_WCHUNK];
+    __shared__ __attribute__((aligned(1024))) char xbuf[H16_NB][H16_XCHUNK];
+    __shared__ float bsh[PW_CO];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wq = wave & 1, wc = wave >> 1;  // pixel half, output-channel half
+    const long p0 = (long)blockIdx.x * H16_P;
+    const int b = blockIdx.y;
+    const _Float16 *src = in + (long)b * in_bs;
+    const int n = (Cin + H16_KC - 1) / H16_KC;
+    const unsigned wbase = __builtin_amdgcn_readfirstlane((unsigned)(size_t)&wbuf[0][0]);
+    const unsigned xbase = __builtin_amdgcn_readfirstlane((unsigned)(size_t)&xbuf[0][0]);
+    // activation piece of this wave: LDS slots 64 wave .. 64 wave + 63 of the chunk's 256 (16 bytes each); slot s holds row
+    // s >> 4, chunk (s & 15) ^ swz(row) -- the lane fetches exactly that
+    const int xrow = 4 * wave + (lane >> 4);
+    const int xch = (lane & 15) ^ (((xrow & 3) << 2) | ((xrow >> 2) & 3));
+    long pix = p0 + 8 * xch;
+    if (pix > HW - 8) pix = HW - 8;  // the plane's last tile: clamped columns are computed and never stored
+    auto dma = [&](int c) __attribute__((always_inline)) {
+        const unsigned slot = (unsigned)(c % H16_NB);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int piece = wave * 2 + i;
+            lds_dma16(wpk + (long)c * H16_WCHUNK + piece * 1024 + lane * 16, wbase + slot * (unsigned)H16_WCHUNK + (unsigned)piece * 1024u);
+        }
+        int row = c * H16_KC + xrow;
+        row = row < Cin ? row : Cin - 1;  // past Cin: any row of the input (its weights are zero)
+        lds_dma16(src + (long)row * HW + pix, xbase + slot * (unsigned)H16_XCHUNK + (unsigned)wave * 1024u);
+    };
+    // transposed reads: read t (k = 8 h + 4 t + 0..3) of pixel block pb; 16-lane group g takes rows 8 (g >> 1) + 4 t + q, pixel
+    // chunks 8 wq + 4 pb + 2 (g & 1) + (p >> 1), lane 4 q + p of the group the 8 bytes at + 8 (p & 1)
+    unsigned xoff[2][2];
+    {
+        const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb) {
+                const int r = 8 * (g >> 1) + 4 * t + q, ch = 8 * wq + 4 * pb + 2 * (g & 1) + (p >> 1);
+                xoff[t][pb] = 256u * r + 16u * (unsigned)(ch ^ (((r & 3) << 2) | ((r >> 2) & 3))) + 8u * (p & 1);
+            }
+    }
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    __shared__ float hsh[HEAD ? PW_CO : 1];  // the output layer's weights (128 global loads per lane in the epilogue spill)
+    bsh[tid] = b2[tid];  // (before the first DMA: the wait hipcc puts behind this load must not see the queue)
+    if (HEAD) hsh[tid] = head_w[tid];
+    // a step needs its chunk landed and leaves the younger ones in flight: 3 pieces per wave and chunk
+#define H16_WAIT(younger_)                                                                                             \
+    do {                                                                                                               \
+        if ((younger_) >= 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                                          \
+        else if ((younger_) == 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");                                     \
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                          \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                             \
+        __builtin_amdgcn_s_barrier();                                                                                  \
+        asm volatile("" ::: "memory");                                                                                 \
+    } while (0)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    dma(0);
+    if (n > 1) dma(1);
+    if (n > 2) dma(2);
+    H16_WAIT((n < 3 ? n : 3) - 1);
+    for (int c = 0; c < n; ++c) {
+        if (c + 3 < n) dma(c + 3);  // (its slot was last read in iteration c - 1: everyone is past that barrier)
+        const unsigned slot = (unsigned)(c % H16_NB);
+        const char *X = &xbuf[0][0] + slot * (unsigned)H16_XCHUNK;
+        f16x8 xb[2];
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb) {
+            const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((h16_lds_ptr)(X + xoff[0][pb])));
+            const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((h16_lds_ptr)(X + xoff[1][pb])));
+            xb[pb] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+        const uint4 *W = (const uint4 *)(&wbuf[0][0] + slot * (unsigned)H16_WCHUNK) + (wc * 4) * 64 + lane;
+#pragma unroll
+        for (int blk = 0; blk < 4; ++blk) {
+            const f16x8 a = __builtin_bit_cast(f16x8, W[blk * 64]);
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb) {
+                if (HEAD) acc[blk][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, xb[pb], acc[blk][pb], 0, 0, 0);
+                else acc[blk][pb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xb[pb], a, acc[blk][pb], 0, 0, 0);
+            }
+        }
+        // chunk c + 1 must have landed; c + 2 and c + 3 may stay in flight
+        const int last = (c + 3 < n ? c + 3 : n - 1);
+        H16_WAIT(last - (c + 1));
+    }
+#undef H16_WAIT
+    const int co0 = wc * 128;
+    if (HEAD) {
+        // C/D layout: column = lane & 31 (pixel), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (output channel); DynamicSegHead's
+        // output layer on layer 4's ReLU, in fp32 as in conv1x1_x3_kernel: layer 4's activation is never rounded or written
+        float *red = (float *)&xbuf[0][0];  // (free: everyone is past the loop's last barrier)
+        float sp[2];
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb) {
+            float a = 0.0f;
+#pragma unroll
+            for (int cb = 0; cb < 4; ++cb) {
+                asm volatile("" : "+v"(a)::"memory");  // (a block's 32 LDS reads at a time: all 256 in flight spill)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int co = co0 + cb * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    a = fmaf(f16_relu(acc[cb][pb][r] + bsh[co]), hsh[co], a);
+                }
+            }
+            sp[pb] = a + __shfl_xor(a, 32);
+        }
+        if (lane < 32) {
+            red[wc * H16_P + wq * 64 + lane] = sp[0];
+            red[wc * H16_P + wq * 64 + 32 + lane] = sp[1];
+        }
+        __syncthreads();
+        if (tid < H16_P && p0 + tid < HW)
+            head_out[(long)b * HW + p0 + tid] = (red[tid] + red[H16_P + tid]) + (head_b ? head_b[0] : 0.0f);
+        return;
+    }
+    // C/D layout with the activation as A: column = lane & 31 (output channel), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    // (pixel): registers 4 g .. 4 g + 3 are pixels 8 g + 4 (lane >> 5) + 0..3 of the lane's channel -- whole inside the plane or
+    // whole outside it (h*w is a multiple of 8)
+    const long obase = (long)b * PW_CO * HW;
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb) {
+        const int co = co0 + cb * 32 + (lane & 31);
+        const float bz = bsh[co];
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const long p = p0 + wq * 64 + pb * 32 + 8 * g + 4 * (lane >> 5);
+                if (p >= HW) continue;
+                f32x4 v = {acc[cb][pb][4 * g] + bz, acc[cb][pb][4 * g + 1] + bz, acc[cb][pb][4 * g + 2] + bz, acc[cb][pb][4 * g + 3] + bz};
+                if (add) v += *(const f32x4 *)(add + (long)co * HW + p);  // layer 1's shared-embedding half: fp32, unrounded
+                if (OUT32) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = relu_out ? f16_relu(v[j]) : v[j];
+                    *(f32x4 *)((float *)out + obase + (long)co * HW + p) = v;
+                    continue;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) v[j] = f16_sat(relu_out ? f16_relu(v[j]) : v[j]);
+                *(f16x4 *)((_Float16 *)out + obase + (long)co * HW + p) = __builtin_convertvector(v, f16x4);
             }
     }
 }
@@ -1225,4 +1477,82 @@ static int x3_impl(const float *in, int64_t in_batch_stride, int B, int Cin, int
     hipLaunchKernelGGL(conv1x1_x3_kernel<2>, grid, dim3(X3_NT), 0, (hipStream_t)stream, in, (long)in_batch_stride, Cin, (long)HW,
                        (const char *)wpk, b2, add, relu_out, out, head_w, head_b, head_out);
     return manet_check_launch("manet_conv1x1_x3_f32");
+}
+
+// ---- head_act="f16": fp16 activations between the stages of a DynamicSegHead -------------------------------------------------
+// depthwise 7x7 + bias + folded bn1 + ReLU, fp16 out = rn16(min(., 65504)); in_f16 != 0: the input planes are fp16 too (layers
+// 2-4), else fp32 (layer 1).  The even-w form only.
+extern "C" int manet_dwconv7x7_bn_relu_f16(const void *in, int in_f16, int B, int C, int h, int w, const float *weight,
+                                           const float *bias, const float *bn_scale, const float *bn_shift, void *out,
+                                           manet_stream_t stream)
+{
+    if (!in) return manet_set_error(MANET_E_INVALID, "in is NULL");
+    if (!weight) return manet_set_error(MANET_E_INVALID, "weight is NULL");
+    if (!out) return manet_set_error(MANET_E_INVALID, "out is NULL");
+    if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || (long)B * C > 65535)
+        return manet_set_error(MANET_E_INVALID, "bad shape B=%d C=%d h=%d w=%d (B*C must be <= 65535)", B, C, h, w);
+    if (w % 2 != 0) return manet_set_error(MANET_E_INVALID, "w=%d must be even (rows of halves are read and written in pairs)", w);
+    if (((size_t)in & 7) != 0 || ((size_t)out & 7) != 0) return manet_set_error(MANET_E_INVALID, "in / out must be 8-byte aligned");
+    const int ntx = (w + DW_TX - 1) / DW_TX, nty = (h + DW_TY - 1) / DW_TY;
+    const int rem = w - (ntx - 1) * DW_TX;  // (the tile plan of manet_dwconv7x7_bn_relu_ex)
+    const bool narrow = ntx >= 2 && rem <= DwNarrow::TX && manet_tune_get(MANET_TUNE_DW_NARROW, 1) != 0;
+    const int nstd = narrow ? (ntx - 1) * nty : ntx * nty;
+    const int ntile = narrow ? nstd + (h + DwNarrow::TY - 1) / DwNarrow::TY : nstd;
+    const int per_item = (B > 1 && (long)ntile * C < 512) ? 1 : 0;
+    const long planes = per_item ? (long)B * C : C;
+    const long nblocks = 8L * ntile * ((planes + 7) / 8);
+    if (nblocks > 0x7fffffffL) return manet_set_error(MANET_E_INVALID, "too many tiles for one launch");
+    dim3 grid((unsigned)nblocks);
+    if (in_f16)
+        hipLaunchKernelGGL(dwconv7x7_bn_relu_f16_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, in, B, C, h, w, weight, bias,
+                           bn_scale, bn_shift, (_Float16 *)out, per_item, ntx, nty, nstd, ntile);
+    else
+        hipLaunchKernelGGL(dwconv7x7_bn_relu_f16_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, in, B, C, h, w, weight, bias,
+                           bn_scale, bn_shift, (_Float16 *)out, per_item, ntx, nty, nstd, ntile);
+    return manet_check_launch("manet_dwconv7x7_bn_relu_f16");
+}
+
+// bytes of the packed fp16 weight image of a [Cin][256] 1x1 layer (manet_conv1x1_f16_pack)
+extern "C" int64_t manet_conv1x1_f16_weight_bytes(int Cin) { return Cin <= 0 ? 0 : (int64_t)((Cin + H16_KC - 1) / H16_KC) * H16_WCHUNK; }
+
+extern "C" int manet_conv1x1_f16_pack(const float *w2t, int Cin, int Cout, void *wpk, manet_stream_t stream)
+{
+    if (!w2t) return manet_set_error(MANET_E_INVALID, "w2t is NULL");
+    if (!wpk) return manet_set_error(MANET_E_INVALID, "wpk is NULL");
+    if (Cin <= 0) return manet_set_error(MANET_E_INVALID, "Cin=%d must be positive", Cin);
+    if (Cout != PW_CO) return manet_set_error(MANET_E_INVALID, "Cout=%d (this kernel is built for %d output channels)", Cout, PW_CO);
+    if (((size_t)wpk & 15) != 0) return manet_set_error(MANET_E_INVALID, "wpk must be 16-byte aligned");
+    const int n = (Cin + H16_KC - 1) / H16_KC;
+    hipLaunchKernelGGL(conv1x1_f16_pack_kernel, dim3((unsigned)(n * 2)), dim3(256), 0, (hipStream_t)stream, w2t, Cin, (uint4 *)wpk, n);
+    return manet_check_launch("manet_conv1x1_f16_pack");
+}
+
+// 1x1 convolution with 256 output channels on the fp16 MFMA (conv1x1_f16_kernel): in [B][Cin][HW] fp16, out [B][256][HW] fp16, or
+// head_w != NULL: the fused fp32 logits head_out [B][HW] (`out` is not written); out_f32 != 0: out is [B][256][HW] fp32, unrounded
+extern "C" int manet_conv1x1_f16(const void *in, int64_t in_batch_stride, int B, int Cin, int64_t HW, const void *wpk,
+                                 const float *b2, const float *add, int Cout, int relu_out, void *out, int out_f32,
+                                 const float *head_w, const float *head_b, float *head_out, manet_stream_t stream)
+{
+    if (!in) return manet_set_error(MANET_E_INVALID, "in is NULL");
+    if (!wpk) return manet_set_error(MANET_E_INVALID, "wpk is NULL");
+    if (!b2) return manet_set_error(MANET_E_INVALID, "b2 is NULL");
+    if (!out && !head_w) return manet_set_error(MANET_E_INVALID, "out is NULL (and no fused output layer: head_w is NULL)");
+    if (head_w && !head_out) return manet_set_error(MANET_E_INVALID, "head_out is NULL");
+    if (B <= 0 || B > 65535 || Cin <= 0 || HW <= 0) return manet_set_error(MANET_E_INVALID, "bad shape B=%d Cin=%d HW=%lld", B, Cin, (long long)HW);
+    if (Cout != PW_CO) return manet_set_error(MANET_E_INVALID, "Cout=%d (this kernel is built for %d output channels)", Cout, PW_CO);
+    if (HW % 8 != 0) return manet_set_error(MANET_E_INVALID, "HW=%lld must be a multiple of 8 (16-byte LDS-DMA rows of halves)", (long long)HW);
+    if (((size_t)wpk & 15) != 0 || ((size_t)in & 15) != 0 || (in_batch_stride & 7) != 0 || ((size_t)out & 15) != 0 || ((size_t)add & 15) != 0)
+        return manet_set_error(MANET_E_INVALID, "in / wpk / out / add must be 16-byte aligned, in_batch_stride a multiple of 8 elements");
+    if (head_w && add) return manet_set_error(MANET_E_INVALID, "add and the fused output layer (head_w) are exclusive");
+    dim3 grid((unsigned)((HW + H16_P - 1) / H16_P), (unsigned)B);
+    if (head_w)
+        hipLaunchKernelGGL(conv1x1_f16_kernel<true>, grid, dim3(H16_NT), 0, (hipStream_t)stream, (const _Float16 *)in, (long)in_batch_stride,
+                           Cin, (long)HW, (const char *)wpk, b2, add, relu_out, out, head_w, head_b, head_out);
+    else if (out_f32)
+        hipLaunchKernelGGL((conv1x1_f16_kernel<false, true>), grid, dim3(H16_NT), 0, (hipStream_t)stream, (const _Float16 *)in,
+                           (long)in_batch_stride, Cin, (long)HW, (const char *)wpk, b2, add, relu_out, out, head_w, head_b, head_out);
+    else
+        hipLaunchKernelGGL(conv1x1_f16_kernel<false>, grid, dim3(H16_NT), 0, (hipStream_t)stream, (const _Float16 *)in, (long)in_batch_stride,
+                           Cin, (long)HW, (const char *)wpk, b2, add, relu_out, out, head_w, head_b, head_out);
+    return manet_check_launch("manet_conv1x1_f16");
 }

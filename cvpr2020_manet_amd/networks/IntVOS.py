@@ -66,6 +66,36 @@ def _pointwise_mode(block=None):
     return _POINTWISE_MODES[mode]
 
 
+# storage of the activations BETWEEN the stages of a DynamicSegHead on the inference fast path:
+#   "f32" : the route as it is (the default);
+#   "f16" : every stage stores rn16(min(relu(.), 65504)) -- fp16, rounded once to nearest even, saturating, a NaN kept; the
+#           depthwise stages keep their fp32 fmaf chains (ops.dwconv7x7_bn_relu_f16), the 256-channel 1x1 stages multiply exact
+#           fp16 x fp16 products of the activation and the folded weight rounded once to fp16 on the fp16 MFMA with fp32
+#           accumulation (ops.conv1x1_f16); layer 1's shared-half term stays fp32 and is added unrounded; layer 4's ReLU and the
+#           output conv stay fused in fp32: logits are fp32 [n, 1, h, w].  Opt-in (IntVOS(cfg, fe, head_act="f16") /
+#           cfg.MODEL_HEAD_ACT / use_head_act); a head that is not eligible (DynamicSegHead._f16_ok) takes the "f32" route, same bits.
+_HEAD_ACT_MODES = ("f32", "f16")
+
+
+def _head_act_mode(value):
+    mode = value.lower() if isinstance(value, str) else value
+    if mode not in _HEAD_ACT_MODES:
+        raise ValueError("head_act=%r ('f32' or 'f16')" % (value,))
+    return mode
+
+
+def use_head_act(module, mode="f16"):
+    """Stamp the activation storage mode on every DynamicSegHead and _split_separable_conv2d under `module` (IntVOS(head_act=...)
+    and the `head_act` property call this; a head built outside an IntVOS takes it directly).  A plain attribute: not a buffer,
+    not in the state dict.  The mode is part of `_folded`'s key: a switch re-folds, and a memoised term of one mode is never
+    used in the other."""
+    mode = _head_act_mode(mode)
+    for m in module.modules():
+        if isinstance(m, (_split_separable_conv2d, DynamicSegHead)):
+            object.__setattr__(m, "_head_act", mode)
+    return module
+
+
 def _train_mode(on):
     """the switch's value: "all" (depthwise, BatchNorm + ReLU and the 1x1 convolutions), "fused" ("all", and a whole
     DynamicSegHead as one op), else bool(on) (True: the depthwise layers)"""
@@ -380,7 +410,8 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
         its weights -- bn2(conv2(x)) == conv2'(x) -- the latter also split at input channel `cs` (forward_shared)."""
         src = [self.bn1.weight, self.bn1.bias, self.bn1.running_mean, self.bn1.running_var, self.bn2.weight,
                self.bn2.bias, self.bn2.running_mean, self.bn2.running_var, self.conv2.weight, self.conv2.bias]
-        key = (cs, _pointwise_mode(self)) + tuple((t.data_ptr(), t._version) if t is not None else None for t in src)
+        act = getattr(self, "_head_act", "f32")
+        key = (cs, _pointwise_mode(self), act) + tuple((t.data_ptr(), t._version) if t is not None else None for t in src)
         hit = getattr(self, "_fold_cache", None)
         if hit is not None and hit[0] == key:
             return hit[1]
@@ -403,6 +434,15 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
                 else:  # ops.conv1x1_mfma
                     val["w2t"], val["w2t_shared"], val["w2t_object"] = w2t, w2t[:cs].contiguous(), w2t[cs:].contiguous()
             val["mode"] = mode
+            if act == "f16" and self.conv2.out_channels == ops.PW_COUT and w2.is_cuda:
+                # head_act="f16": the folded weight (fp32, as above) rounded ONCE to fp16 and packed -- whole, and the shared /
+                # object slices of forward_shared.  A weight that is not finite in fp16 makes the block ineligible: no "hw"
+                # (one host read per fold; folds happen before a driver forks its streams or captures: prepare_bank)
+                if bool(torch.isfinite(w2.half()).all()):
+                    w2t = w2.reshape(w2.shape[0], w2.shape[1]).t().contiguous()
+                    val["hw"] = ops.HalfWeight(w2t)
+                    if 0 < cs < w2t.shape[0]:
+                        val["hw_shared"], val["hw_object"] = ops.HalfWeight(w2t[:cs]), ops.HalfWeight(w2t[cs:])
         object.__setattr__(self, "_fold_cache", (key, val))  # plain attribute: not a buffer, not in the state dict
         return val
 
@@ -421,11 +461,42 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
         z = F.conv2d(y, k[w], k["b2"] if bias else None)
         return z.relu_() if relu else z
 
-    def forward(self, x, relu_in=False, defer_relu=False, head=None):
+    def _f16_block_ok(self, cs=0):
+        """the block can run on the f16 kernels (head_act="f16"): stamped, a 7x7 depthwise conv with padding 3, 256 output
+        channels, fp32 GPU parameters, and folded weights that are finite in fp16 (with their slices at `cs`, when cs > 0)"""
+        c1 = self.conv1
+        if not (getattr(self, "_head_act", "f32") == "f16" and c1.kernel_size == (7, 7) and c1.padding == (3, 3)
+                and c1.stride == (1, 1) and c1.dilation == (1, 1) and c1.groups == c1.in_channels == c1.out_channels
+                and c1.padding_mode == "zeros" and self.conv2.out_channels == ops.PW_COUT and self.conv2.kernel_size == (1, 1)
+                and c1.weight.is_cuda and c1.weight.dtype == torch.float32 and self.conv2.weight.dtype == torch.float32):
+            return False
+        k = self._folded(cs)
+        return "hw" in k and (cs == 0 or "hw_object" in k)
+
+    def _forward_f16(self, x, head=None):
+        """the block on fp16 activations (head_act="f16"; the caller checked DynamicSegHead._f16_ok): x fp32 (layer 1) or fp16 ->
+        fp16, or with head = (weight, bias) of the output layer the fp32 logits"""
+        k = self._folded()
+        y = ops.dwconv7x7_bn_relu_f16(x, self.conv1.weight, self.conv1.bias, scale=k["scale1"], shift=k["shift1"])
+        if head is not None:
+            return ops.conv1x1_f16(y, k["hw"], k["b2"], head_weight=head[0], head_bias=head[1])
+        return ops.conv1x1_f16(y, k["hw"], k["b2"], relu_out=True)
+
+    def _shared_term_f16(self, shared, k, cs):
+        """layer 1's shared-half term in head_act="f16": the fp16 contraction of the shared channels' fp16 depthwise output,
+        left in fp32, unrounded; shared [b, cs, h, w] fp32 -> [b, 256, h, w] fp32"""
+        w1, b1 = self.conv1.weight, self.conv1.bias
+        s1 = ops.dwconv7x7_bn_relu_f16(shared, w1[:cs], None if b1 is None else b1[:cs], scale=k["scale1"][:cs], shift=k["shift1"][:cs])
+        return ops.conv1x1_f16(s1, k["hw_shared"], k["b2_zero"], out_f32=True)
+
+    def forward(self, x, relu_in=False, defer_relu=False, head=None, act16=False):
         """relu_in / defer_relu (inference fast path only, used by DynamicSegHead): the block's last ReLU is left to the
         NEXT block, whose fused depthwise kernel reads its input through max(x, 0) -- one elementwise pass over the
         activation less per block, same values.  head = (weight, bias) of DynamicSegHead's output layer: fused into this
-        block's 1x1 kernel when it runs on the MFMA path (returns [B, 1, h, w]), else applied behind it."""
+        block's 1x1 kernel when it runs on the MFMA path (returns [B, 1, h, w]), else applied behind it.
+        act16 (DynamicSegHead, head_act="f16" on an eligible head): the f16 kernels, fp16 in and out."""
+        if act16:
+            return self._forward_f16(x, head)
         if self._fast(x):
             k = self._folded()
             x = ops.dwconv7x7_bn_relu(x, self.conv1.weight, self.conv1.bias, scale=k["scale1"], shift=k["shift1"],
@@ -449,7 +520,7 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
         x = self.relu2(self.bn2(self.conv2(x)))
         return x
 
-    def forward_shared(self, shared, per_object, defer_relu=False, memo=None):
+    def forward_shared(self, shared, per_object, defer_relu=False, memo=None, act16=False):
         """The block applied to cat([shared repeated n times, per_object], 1) without building that tensor
         (IntVOS.py:665-670 repeats the C-channel embedding once per object): the depthwise stage and the
         1x1 stage are linear in the channel groups, so the shared group is processed once.
@@ -463,6 +534,15 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
         k = self._folded(cs)
         scale, shift = k["scale1"], k["shift1"]
         w1, b1 = self.conv1.weight, self.conv1.bias
+        if act16:  # head_act="f16": the general three-launch form on the f16 kernels; the term is fp32, memoised as ever
+            stamp = _memo_stamp(self, k)
+            term = memo.get("term") if (memo is not None and memo.get("k") is k and memo.get("stamp") == stamp) else None
+            if term is None:
+                term = self._shared_term_f16(shared, k, cs)
+                if memo is not None:
+                    memo["k"], memo["term"], memo["stamp"] = k, term, stamp
+            p1 = ops.dwconv7x7_bn_relu_f16(per_object, w1[cs:], None if b1 is None else b1[cs:], scale=scale[cs:], shift=shift[cs:])
+            return ops.conv1x1_f16(p1, k["hw_object"], k["b2"], relu_out=True, add=term)
         p1 = ops.dwconv7x7_bn_relu(per_object, w1[cs:], b1[cs:], scale=scale[cs:], shift=shift[cs:])
         split = "sw_object" in k and ops.conv1x1_split_ok(p1, self.conv2.out_channels)
         mfma = not split and "w2t_object" in k and ops.conv1x1_mfma_ok(p1, self.conv2.out_channels)
@@ -539,12 +619,30 @@ class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
         if _train_mode(train_kernels):
             use_train_kernels(self, train_kernels)
 
-    def _tail(self, x):
+    def _f16_ok(self, h, w, cs=0):
+        """head_act="f16" applies to this head at an [h, w] grid (decided from shapes and modes, before any launch; the caller
+        checked today's fast-path conditions: eval mode, GPU, no grad, fp32 input): the four blocks are 7x7 depthwise with 256
+        output channels and fp16-finite folded weights, the output layer is a 1x1 conv to one channel, w is even (rows of halves
+        move in pairs) and h*w a multiple of 8 (16-byte rows of halves).  cs: the shared channels of forward_shared."""
+        if getattr(self, "_head_act", "f32") != "f16" or w % 2 != 0 or (h * w) % 8 != 0 or h * w < 8:
+            return False
+        c = self.conv
+        if not (c.kernel_size == (1, 1) and c.out_channels == 1 and c.in_channels == ops.PW_COUT and c.stride == (1, 1)
+                and c.padding == (0, 0) and c.weight.is_cuda and c.weight.dtype == torch.float32):
+            return False
+        return (0 <= cs < self.layer1.conv1.in_channels and self.layer1._f16_block_ok(cs)
+                and all(l.conv1.in_channels == ops.PW_COUT and l._f16_block_ok() for l in (self.layer2, self.layer3, self.layer4)))
+
+    def _tail(self, x, act16=False):
         """layers 2-4 + the 1x1 output conv on the inference fast path; x = layer1's output.  r5: every block's last ReLU
         is applied in the epilogue of its own 1x1 kernel, where it is free -- r2-r4 left it to the NEXT block's depthwise
         kernel (`relu_in`, from the days the 1x1 stage was the framework's GEMM and a ReLU meant a pass): 60 v_max per
         staged tile less (0.5 us of 47 at [3,256,120,214]: that kernel hides them).  Same values either way.  (`relu_in` /
-        `defer_relu` remain for blocks whose 1x1 stage falls back to the framework's convolution.)"""
+        `defer_relu` remain for blocks whose 1x1 stage falls back to the framework's convolution.)
+        act16 (head_act="f16", an eligible head): x is fp16, every block runs the f16 kernels, the logits are fp32."""
+        if act16:
+            x = self.layer3(self.layer2(x, act16=True), act16=True)
+            return self.layer4(x, head=(self.conv.weight, self.conv.bias), act16=True)
         x = self.layer2(x)
         x = self.layer3(x)
         if self.conv.kernel_size == (1, 1) and self.conv.out_channels == 1:
@@ -555,7 +653,8 @@ class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
 
     def forward(self, x):
         if self.layer1._fast(x):
-            return self._tail(self.layer1(x))
+            act16 = x.dim() == 4 and self._f16_ok(x.shape[2], x.shape[3])
+            return self._tail(self.layer1(x, act16=act16), act16=act16)
         if (self.training or torch.is_grad_enabled()) and _train_fused_ok(self, x):
             return ops.dynamic_seghead_train(self, x)  # training route "fused" (use_train_kernels): one autograd node
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
@@ -568,7 +667,10 @@ class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
     def forward_shared(self, shared, per_object, memo=None):
         """forward(cat([shared.repeat(n,1,1,1), per_object], 1)) without materialising the input; memo: see
         _split_separable_conv2d.forward_shared"""
-        return self._tail(self.layer1.forward_shared(shared, per_object, memo=memo))
+        act16 = (shared.dim() == 4 and shared.dtype == torch.float32 and per_object.dtype == torch.float32
+                 and shared.shape[1] + per_object.shape[1] == self.layer1.conv1.in_channels
+                 and self._f16_ok(shared.shape[2], shared.shape[3], shared.shape[1]))
+        return self._tail(self.layer1.forward_shared(shared, per_object, memo=memo, act16=act16), act16=act16)
 
 
 def _run_head(head, embedding_chw, per_object, memo=None):
@@ -635,7 +737,7 @@ class IntVOS(nn.Module):
     """reference IntVOS.py:530-764: same constructor, methods, dict conventions, state-dict keys."""
 
     def __init__(self, cfg, feature_extracter, compute=None, emb_dtype=None, pointwise=None, cache_frames=None,
-                 train_kernels=None, train_match=None, local_volume_dtype=None, train_inputs=None):
+                 train_kernels=None, train_match=None, local_volume_dtype=None, train_inputs=None, head_act=None):
         """cfg, feature_extracter: as the reference.  The rest is optional and this implementation's only (default: the
         cfg's MODEL_MATCH_COMPUTE / MODEL_EMB_DTYPE / MODEL_HEAD_POINTWISE / MODEL_CACHE_FRAMES when it has them, else
         "f32" / "f32" / "f32" / True):
@@ -668,7 +770,13 @@ class IntVOS(nn.Module):
                         bits as the fused kernel | "f16" every normalised window distance rounded once to half: half the bytes,
                         twice the pairs under `local_volume_cache_bytes`; a local map then differs from the "f32" one by at most
                         min(2^-12, 2^-11 * value), and 1.0 stays 1.0.  Readable and assignable (`model.local_volume_dtype`);
-                        assigning another value drops the cached volumes"""
+                        assigning another value drops the cached volumes
+          head_act      storage of the activations between the stages of the DynamicSegHeads in inference: "f32" (default; cfg's
+                        MODEL_HEAD_ACT when it has it) the route as it is | "f16" fp16, rounded once per stage and saturating, the
+                        256-channel 1x1 stages on the fp16 MFMA with fp32 accumulation, logits fp32 as ever (see _HEAD_ACT_MODES);
+                        a head or grid that is not eligible (odd w, h*w not a multiple of 8, another width, IntSegHead) takes the
+                        "f32" route with the same bits.  Readable and assignable (`model.head_act`); assigning another value
+                        drops the heads' memoised terms"""
         super().__init__()
         set_cfg(cfg)
         self.cfg = cfg
@@ -724,6 +832,9 @@ class IntVOS(nn.Module):
         for m in self.modules():  # this model's 1x1 mode (not a process-wide switch: two models may differ)
             if isinstance(m, _split_separable_conv2d):
                 object.__setattr__(m, "_pw_mode", self.pointwise)
+        # (a plain attribute: not a buffer, not in the state dict)
+        self._head_act = _head_act_mode(head_act if head_act is not None else getattr(cfg, "MODEL_HEAD_ACT", "f32"))
+        use_head_act(self, self._head_act)
         tk = train_kernels if train_kernels is not None else getattr(cfg, "MODEL_TRAIN_KERNELS", False)
         self.train_kernels = _train_mode(tk)
         use_train_kernels(self, self.train_kernels)
@@ -743,6 +854,19 @@ class IntVOS(nn.Module):
         if mode != self._local_volume_dtype:
             self.invalidate_local_volumes()  # one cache never mixes storage types
         self._local_volume_dtype = mode
+
+    @property
+    def head_act(self):
+        """ "f32" or "f16": the storage of the activations between the stages of the DynamicSegHeads (see the constructor)"""
+        return self._head_act
+
+    @head_act.setter
+    def head_act(self, value):
+        mode = _head_act_mode(value)
+        if mode != self._head_act:
+            self.drop_head_memos()  # a term made in one mode is never used in the other (the re-fold drops it as well)
+        self._head_act = mode
+        use_head_act(self, mode)
 
     def _prepared_bank(self, seq_name, ref_emb_chw, ref_label, ref_emb_hwc, ref_lab_flat, n_ids):
         """The sorted / packed memory bank of the annotated frame, reused while the caller keeps passing the SAME
@@ -890,8 +1014,10 @@ class IntVOS(nn.Module):
             return 0
         layer, cs = head.layer1, int(embeddings.shape[1])
         k = layer._folded(cs)
-        if (k.get("mode") != "f32" or "w2t_shared" not in k or layer.conv1.in_channels != cs + 3
-                or layer.conv2.out_channels != ops.PW_COUT or layer.conv1.kernel_size != (7, 7)):
+        # head_act="f16" on an eligible head and grid: the term of THAT route (the f16 kernels' fp32 term)
+        act16 = len(embeddings.shape) == 4 and head._f16_ok(int(embeddings.shape[2]), int(embeddings.shape[3]), cs)
+        if not act16 and (k.get("mode") != "f32" or "w2t_shared" not in k or layer.conv1.in_channels != cs + 3
+                          or layer.conv2.out_channels != ops.PW_COUT or layer.conv1.kernel_size != (7, 7)):
             return 0
         stamp = _memo_stamp(layer, k)
         w1, b1 = layer.conv1.weight, layer.conv1.bias
@@ -910,8 +1036,11 @@ class IntVOS(nn.Module):
         for i0 in range(0, len(todo), batch):
             part = todo[i0:i0 + batch]
             x = torch.stack([e if e.dtype == torch.float32 else e.float() for e, _ in part])
-            s1 = ops.dwconv7x7_bn_relu(x, w1[:cs], None if b1 is None else b1[:cs], scale=k["scale1"][:cs], shift=k["shift1"][:cs])
-            terms = ops.conv1x1_mfma(s1, k["w2t_shared"], k["b2_zero"])  # [b, 256, h, w]
+            if act16:
+                terms = layer._shared_term_f16(x, k, cs)
+            else:
+                s1 = ops.dwconv7x7_bn_relu(x, w1[:cs], None if b1 is None else b1[:cs], scale=k["scale1"][:cs], shift=k["shift1"][:cs])
+                terms = ops.conv1x1_mfma(s1, k["w2t_shared"], k["b2_zero"])  # [b, 256, h, w]
             for j, (_, memo) in enumerate(part):
                 memo["k"], memo["term"], memo["stamp"] = k, terms[j:j + 1], stamp
             done += len(part)
@@ -1411,7 +1540,9 @@ class IntVOS(nn.Module):
                            and nn_features_n.numel() == h * w * n_ids and prev_frame_nn_features_n.numel() == h * w * n_ids)
             if (native_maps and isinstance(dynamic_seghead, DynamicSegHead) and not dynamic_seghead.training
                     and not torch.is_grad_enabled()  # (eval() with grad mode on: the literal, differentiable head below -- ADVICE r5)
-                    and dynamic_seghead.layer1.conv1.kernel_size == (7, 7) and (h * w) % 4 == 0):
+                    and dynamic_seghead.layer1.conv1.kernel_size == (7, 7) and (h * w) % 4 == 0
+                    # (head_act="f16": there is no fp16-output form of the fused layer-1 kernel -- the general route below)
+                    and not dynamic_seghead._f16_ok(h, w, int(current_frame_embedding[n].shape[0]))):
                 # layer 1 straight from the two maps and the labels (r5): input assembly + per-object depthwise + its 1x1 + the
                 # (memoised) shared half + ReLU in one launch; layers 2-4 as ever
                 emb_f = current_frame_embedding[n]

@@ -1067,6 +1067,97 @@ def conv1x1_split(x, weight, b2, relu_out=False, add=None, head_weight=None, hea
     return hout if head_weight is not None else out
 
 
+F16_MAX = 65504.0  # the largest finite fp16: where the f16 head's stores saturate
+
+
+def dwconv7x7_bn_relu_f16(x, weight, bias=None, bn=None, scale=None, shift=None):
+    """dwconv7x7_bn_relu (relu on) with the output stored as fp16 (manet_dwconv7x7_bn_relu_f16; head_act="f16"): the same fp32
+    fmaf chain on the input widened to fp32, then rn16(min(., 65504)) -- the fp32 kernel's result saturated and rounded once
+    (a NaN stays a NaN).  x [B, C, h, w] fp32 (layer 1) or fp16 (layers 2-4), w even -> [B, C, h, w] fp16."""
+    _refuse_autograd("dwconv7x7_bn_relu_f16", x, weight, bias, scale, shift)
+    _need_gpu(x, "x")
+    if x.dtype != torch.float16:
+        x = x.float()
+    x = x.contiguous()
+    B, C, h, w = x.shape
+    if tuple(weight.shape) != (C, 1, 7, 7):
+        raise ValueError("weight must be [C, 1, 7, 7]")
+    wt = weight.detach().float().contiguous()
+    if bn is not None:
+        scale, shift = fold_bn(bn)
+    if scale is not None:
+        scale, shift = scale.float().contiguous(), shift.float().contiguous()
+    bz = None if bias is None else bias.detach().float().contiguous()
+    out = torch.empty((B, C, h, w), dtype=torch.float16, device=x.device)
+    with _on(x.device):
+        _lib.call("manet_dwconv7x7_bn_relu_f16", x.data_ptr(), int(x.dtype == torch.float16), B, C, h, w, wt.data_ptr(), _ptr(bz),
+                  _ptr(scale), _ptr(shift), out.data_ptr(), _stream_ptr(x.device))
+    return out
+
+
+class HalfWeight:
+    """A 1x1 layer's folded weight rounded once to fp16 and packed for conv1x1_f16 (manet_conv1x1_f16_pack): the MFMA operand
+    image, 8 KiB per 16 input channels.  `cin` input channels, PW_COUT output channels.  The caller checks that the folded
+    weights are finite in fp16 (networks/IntVOS.py: a block whose weights are not is ineligible)."""
+
+    def __init__(self, w2t):
+        lib = _lib.load()
+        _need_gpu(w2t, "w2t")
+        w2t = w2t.detach().float().contiguous()
+        if w2t.dim() != 2 or w2t.shape[1] != PW_COUT:
+            raise ValueError("w2t must be [Cin, %d] (ops.fold_pointwise)" % PW_COUT)
+        self.cin = int(w2t.shape[0])
+        self.packed = torch.empty(int(lib.manet_conv1x1_f16_weight_bytes(self.cin)), dtype=torch.uint8, device=w2t.device)
+        with _on(w2t.device):
+            _lib.call("manet_conv1x1_f16_pack", w2t.data_ptr(), self.cin, PW_COUT, self.packed.data_ptr(), _stream_ptr(w2t.device))
+
+
+def conv1x1_f16_ok(x, cout):
+    """shapes the fp16 1x1 kernel takes: 256 output channels, any Cin, h*w a multiple of 8 (16-byte LDS-DMA rows of halves)"""
+    return cout == PW_COUT and x.dim() == 4 and x.shape[1] >= 1 and (x.shape[2] * x.shape[3]) % 8 == 0 and x.shape[2] * x.shape[3] >= 8
+
+
+def conv1x1_f16(x, weight, b2, relu_out=False, add=None, head_weight=None, head_bias=None, out_f32=False):
+    """conv2 -> bn2 [-> relu2] of a _split_separable_conv2d block on fp16 activations (manet_conv1x1_f16; head_act="f16"): exact
+    fp16 x fp16 products on the fp16 MFMA with fp32 accumulation, an fp32 epilogue (+ b2, + add, ReLU) and one rounding at the
+    store, rn16(min(., 65504)).  x [B, Cin, h, w] fp16; weight a HalfWeight; b2 [256] fp32 -> [B, 256, h, w] fp16.
+    add [1, 256, h, w] (or [256, h, w]) fp32: added unrounded to every batch entry before relu_out (layer 1's shared half).
+    head_weight / head_bias: DynamicSegHead's output layer fused in fp32 (see conv1x1_mfma) -> [B, 1, h, w] fp32.
+    out_f32: the result leaves as fp32, unrounded -- layer 1's shared-half term, which a later call takes as `add`."""
+    _refuse_autograd("conv1x1_f16", x, b2, add, head_weight, head_bias)
+    _need_gpu(x, "x")
+    if not isinstance(weight, HalfWeight):
+        raise TypeError("weight must be an ops.HalfWeight")
+    if x.dtype != torch.float16:
+        raise ValueError("x must be fp16 (the f16 depthwise kernel's output)")
+    x = x.contiguous()
+    B, cin, h, w = x.shape
+    if cin != weight.cin or b2.numel() != PW_COUT:
+        raise ValueError("x has %d channels, the packed weight %d; b2 must be [%d]" % (cin, weight.cin, PW_COUT))
+    if not conv1x1_f16_ok(x, PW_COUT):
+        raise ValueError("conv1x1_f16 needs h*w to be a multiple of 8")
+    b2 = b2.detach().float().contiguous()
+    if add is not None:
+        if add.numel() != PW_COUT * h * w:
+            raise ValueError("add must be [1, %d, h, w]" % PW_COUT)
+        add = add.detach().float().contiguous()
+    hw = hb = hout = out = None
+    if head_weight is not None:
+        if head_weight.numel() != PW_COUT:
+            raise ValueError("head_weight must be [1, %d, 1, 1]" % PW_COUT)
+        if add is not None:
+            raise ValueError("add and the fused output layer are exclusive")
+        hw = head_weight.detach().float().contiguous()
+        hb = None if head_bias is None else head_bias.detach().float().contiguous()
+        hout = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
+    else:
+        out = torch.empty((B, PW_COUT, h, w), dtype=torch.float32 if out_f32 else torch.float16, device=x.device)
+    with _on(x.device):
+        _lib.call("manet_conv1x1_f16", x.data_ptr(), cin * h * w, B, cin, h * w, weight.packed.data_ptr(), b2.data_ptr(), _ptr(add),
+                  PW_COUT, int(bool(relu_out)), _ptr(out), int(bool(out_f32)), _ptr(hw), _ptr(hb), _ptr(hout), _stream_ptr(x.device))
+    return hout if head_weight is not None else out
+
+
 def relu_conv1x1_c1(x, weight, bias=None, relu_in=True):
     """DynamicSegHead's output layer in one pass over the activation (IntVOS.py:519,525): Conv2d(C, 1, 1) applied to
     max(x, 0) (relu_in) or to x.  x [B, C, h, w] fp32, weight [1, C, 1, 1], bias [1] or None -> [B, 1, h, w]."""

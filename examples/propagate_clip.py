@@ -66,13 +66,13 @@ class StandInEncoder(nn.Module):
         return self.net(x)
 
 
-def build_model(dev, compute=None, emb_dtype=None, pointwise=None, seed=0, local_volume_dtype=None):
+def build_model(dev, compute=None, emb_dtype=None, pointwise=None, seed=0, local_volume_dtype=None, head_act=None):
     from cvpr2020_manet_amd.config import make_cfg
     from cvpr2020_manet_amd.networks.IntVOS import IntVOS
     torch.manual_seed(seed)
     cfg = make_cfg(["--TEST_MODE", "True"])
     model = IntVOS(cfg, StandInEncoder(cfg.MODEL_ASPP_OUTDIM), compute=compute, emb_dtype=emb_dtype,
-                   pointwise=pointwise, local_volume_dtype=local_volume_dtype).to(dev).eval()
+                   pointwise=pointwise, local_volume_dtype=local_volume_dtype, head_act=head_act).to(dev).eval()
     return cfg, model
 
 
@@ -508,10 +508,30 @@ def against_f32_volumes(model, clip, emb, session=0):
     return out
 
 
+def against_f32_head(model, clip):
+    """The same clip in the same process with the fp32 head (model.head_act = "f32"): what fp16 activations between the head's
+    stages move in the logits and, at full resolution, in the masks, over every propagated frame of one interaction round.  A
+    measurement of THIS model -- the encoder and head weights here are stand-ins: the flip fraction is not a trained model's.
+    Runs after the timed regions; leaves the model in its own mode."""
+    def run():
+        logits = {}
+        return logits, clip.one_round(keep_logits=logits)
+
+    got, got_masks = run()
+    mode = model.head_act
+    model.head_act = "f32"  # (drops the heads' memoised terms)
+    want, want_masks = run()
+    model.head_act = mode
+    diff = torch.cat([(got[k] - want[k]).reshape(-1) for k in want])
+    return {"logit_max_abs_err": float(diff.abs().max()), "logit_rms_err": float(diff.double().pow(2).mean().sqrt()),
+            "logit_max_abs": max(float(want[k].abs().max()) for k in want),
+            "mask_flip_fraction": float((got_masks != want_masks).float().mean())}
+
+
 def run_single(args, dev, pointwise=None, want_graph=False, want_stages=False, bank=None, bank_frames=None):
     """one process, one GPU: eager (and graph) frames/s of the end-to-end propagated frame"""
     cfg, model = build_model(dev, args.compute, args.emb_dtype, pointwise if pointwise is not None else args.pointwise,
-                             local_volume_dtype=getattr(args, "volume_dtype", None))
+                             local_volume_dtype=getattr(args, "volume_dtype", None), head_act=getattr(args, "head_act", None))
     with torch.no_grad():
         # (the producer's fused epilogue: embeddings + every frame's operands from one launch per extraction batch)
         emb = synthetic_clip(model, dev, args.frames, args.height, args.width, args.objects, packed=not args.no_packed)
@@ -583,6 +603,8 @@ def run_single(args, dev, pointwise=None, want_graph=False, want_stages=False, b
                         "graph_masks_equal_eager": bool(torch.equal(gfinal, final))})
         if model.local_volume_dtype != "f32" and vol_pairs:
             res["local_volumes"].update(against_f32_volumes(model, clip, emb, session=getattr(args, "session", 0)))
+        if model.head_act != "f32":
+            res["head_act"] = dict(against_f32_head(model, clip), mode=model.head_act)
     return res, clip, final
 
 
@@ -765,6 +787,10 @@ def parse_args(argv=None):
                          "local maps within min(2^-12, 2^-11 * value) of f32's.  An f16 run also repeats the round (and the --session) "
                          "on f32 volumes after the timed regions, for logit_max_abs_diff / mask_flip_fraction: about twice the "
                          "wall time, the timed figures are not touched")
+    ap.add_argument("--head-act", type=str, default=None, choices=["f32", "f16"],
+                    help="storage of the activations between the stages of the propagation heads (model.head_act): f16 = fp16, rounded "
+                         "once per stage, the 1x1 stages on the fp16 MFMA.  An f16 run also repeats the round with the fp32 head after "
+                         "the timed regions, for logit_max_abs_err / logit_rms_err / logit_max_abs / mask_flip_fraction")
     ap.add_argument("--two-streams", action="store_true",
                     help="also time the round with the forward and the backward half of the chain on two HIP streams")
     ap.add_argument("--stages", action="store_true", help="per-stage microseconds of a propagated frame (HIP events)")

@@ -649,6 +649,33 @@ int manet_conv1x1_x3_f32(const float *in, int64_t in_batch_stride, int B, int Ci
                          const float *add, int Cout, int relu_out, float *out, const float *head_w, const float *head_b,
                          float *head_out, manet_stream_t stream);
 
+/* fp16 ACTIVATIONS between the stages of a DynamicSegHead (networks/IntVOS.py: head_act="f16", opt-in).  Every stored
+ * activation is post-ReLU and is rounded ONCE, to nearest even, from the stage's fp32 result saturated at 65504:
+ * rn16(min(., 65504)); a NaN stays a NaN; subnormals are kept.  All four entry points validate before anything is launched
+ * (MANET_E_INVALID, the text names the argument), allocate nothing and never synchronise.
+ *   manet_dwconv7x7_bn_relu_f16: manet_dwconv7x7_bn_relu_ex's stage with relu on: out [B][C][h][w] fp16 =
+ *     rn16(min(relu(fmaf(acc + bias, bn_scale, bn_shift)), 65504)), acc the SAME fp32 fmaf chain (ky outer, kx inner) on the
+ *     input widened to fp32 -- the fp32 kernel's result, saturated and rounded.  in [B][C][h][w] fp32 (in_f16 == 0: layer 1) or
+ *     fp16 (in_f16 != 0: layers 2-4); w even; in / out 8-byte aligned; bias / bn_scale / bn_shift may be NULL.
+ *   manet_conv1x1_f16_weight_bytes(Cin) / manet_conv1x1_f16_pack: w2t [Cin][256] fp32 (as for manet_conv1x1_f32: bn2 folded in
+ *     fp32) -> `wpk`, every weight rounded once to fp16, as the MFMA operand image [16-channel chunk][co block 8][lane 64] x 16
+ *     bytes (8 KiB per 16 input channels, zero past Cin); once per fold; wpk 16-byte aligned.  The caller checks that the
+ *     folded weights are finite in fp16.
+ *   manet_conv1x1_f16: in [B][Cin][HW] fp16 (batch stride in_batch_stride elements, a multiple of 8; 0 = one tensor for every
+ *     batch item), any Cin >= 1, HW a multiple of 8, Cout = 256; exact fp16 x fp16 products summed in fp32 accumulators
+ *     (v_mfma_f32_32x32x16_f16), then in fp32: + b2 [256], + add [256][HW] fp32 (NULL = none; added unrounded), max(., 0) if
+ *     relu_out; out [B][256][HW] fp16 = rn16(min(., 65504)), or with out_f32 != 0 fp32, unrounded (layer 1's shared-half term,
+ *     which a later call takes as `add`).  head_w != NULL (exclusive with add): DynamicSegHead's output layer
+ *     fused as in manet_conv1x1_head_f32, in fp32 on the unrounded ReLU output -- head_out [B][HW] fp32, `out` is not written.
+ *     in / wpk / out / add 16-byte aligned. */
+int manet_dwconv7x7_bn_relu_f16(const void *in, int in_f16, int B, int C, int h, int w, const float *weight, const float *bias,
+                                const float *bn_scale, const float *bn_shift, void *out, manet_stream_t stream);
+int64_t manet_conv1x1_f16_weight_bytes(int Cin);
+int manet_conv1x1_f16_pack(const float *w2t, int Cin, int Cout, void *wpk, manet_stream_t stream);
+int manet_conv1x1_f16(const void *in, int64_t in_batch_stride, int B, int Cin, int64_t HW, const void *wpk, const float *b2,
+                      const float *add, int Cout, int relu_out, void *out, int out_f32, const float *head_w, const float *head_b,
+                      float *head_out, manet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Training path: what torch.autograd does for the reference's pure-PyTorch path
  * (train_stage1.py:126-156 back-propagates through IntVOS.forward) and what
