@@ -950,6 +950,145 @@ __global__ __launch_bounds__(H16_NT, 3) void conv1x1_f16_kernel(const _Float16 *
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// DynamicSegHead layer 1, PER-OBJECT half, head_act="f16", ONE launch: the depthwise 7x7 + bn1 + relu1 of the Cp <= 4 per-object
+// channels (fp32 planes in, rounded to fp16 as dwconv7x7_bn_relu_f16_kernel<false> stores them) -> their 1x1 (Cp -> 256, bn2 folded)
+// + the shared half's fp32 term + relu2 -> the fp16 activation, as conv1x1_f16_kernel<false> stores it:
+//   d_c  = rn16(min(relu(fmaf(taps_c + b1[c], scale1[c], shift1[c])), 65504)),  taps_c = the fmaf chain (ky outer, kx inner) from 0
+//   acc  = v_mfma_f32_32x32x16_f16 on a zero accumulator: d_c in k slots 0 .. Cp-1, zeros in the others, the weights from the packed
+//          HalfWeight image's one chunk (conv1x1_f16_kernel clamps its rows past Cin onto row Cin - 1 against zero weights: products
+//          of +0 there and here, the same addends into the same instruction)
+//   out[o][co][p] = rn16(min(relu?((acc + b2[co]) + term[co][p]), 65504))
+// -- the two kernels' composition operation for operation: the same bits.  What it saves is the general kernel's shape: a K = 256
+// pipeline (DMA ring, barriers, 128 x 256 tiles) run for 3 live rows, the term fetched once per OBJECT (26 MB each), and the [n, Cp]
+// fp16 planes' round trip through a launch of their own.
+// A workgroup owns 64 consecutive pixels of the flattened plane x all 256 output channels (wave = channel quarter: two 32-channel
+// blocks x two 32-pixel blocks) and WALKS THE OBJECTS: its 64 KiB of the term are loaded once, 16 x 16 bytes per lane, all in flight
+// before anything else, and stay in 64 registers; per object a lane issues 4 MFMAs and 16 8-byte stores.  Activation as the A
+// operand, as in conv1x1_f16_kernel: a lane owns an output channel and 4 consecutive pixels per register quad (h*w is a multiple of
+// 8: a quad is inside the plane or outside it as a whole; the last tile's term loads are clamped and its outside quads never stored).
+// The depthwise stage runs once per tile and object, its taps read straight from the planes (they are 1.4 % of the stage's bytes and
+// L2 hits after a tile's first touch; the loads go out behind the term's and land with it), split (object, channel) per wave, and
+// reaches the MFMA lanes through a 4 KiB LDS table of L16_OG objects at a time.
+constexpr int L16_P = 64, L16_NT = 256, L16_OG = 8;
+__global__ __launch_bounds__(L16_NT, 3) void head_layer1_object_f16_kernel(const float *__restrict__ planes, int n, int Cp, int h, int w,
+                                                                        const float *__restrict__ w1, const float *__restrict__ b1,
+                                                                        const float *__restrict__ sc1, const float *__restrict__ sh1,
+                                                                        const uint4 *__restrict__ wpk, const float *__restrict__ b2,
+                                                                        const float *__restrict__ term, int relu_out,
+                                                                        _Float16 *__restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) _Float16 dsh[L16_OG][L16_P][4];  // d_0 .. d_3 of a pixel: one 8-byte read
+    const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int HW = h * w, p0 = blockIdx.x * L16_P;
+    const int co0 = wave * 64;
+    f32x4 tv[2][2][4];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int pb = 0; pb < 2; ++pb)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                tv[cb][pb][g] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                if (term) {  // (uniform)
+                    int p = p0 + pb * 32 + 8 * g + 4 * lh;
+                    p = p < HW - 4 ? p : HW - 4;
+                    tv[cb][pb][g] = *(const f32x4 *)(term + (long)(co0 + cb * 32 + l31) * HW + p);
+                }
+            }
+    f16x8 wf[2];
+    float bz[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+        wf[cb] = __builtin_bit_cast(f16x8, wpk[(wave * 2 + cb) * 64 + lane]);
+        bz[cb] = b2[co0 + cb * 32 + l31];
+    }
+    // the lane's pixel in the depthwise stage (a clamped one past the plane: computed, never stored)
+    const int pd = p0 + lane < HW ? p0 + lane : HW - 1;
+    const int yd = pd / w, xd = pd - yd * w;
+    for (int o0 = 0; o0 < n; o0 += L16_OG) {
+        const int ng = n - o0 < L16_OG ? n - o0 : L16_OG;
+        for (int oc = wave; oc < ng * Cp; oc += L16_NT / 64) {  // (object, channel): uniform per wave
+            const int ol = oc / Cp, c = oc - ol * Cp;
+            const char *src = (const char *)(planes + ((long)(o0 + ol) * Cp + c) * HW);
+            const float *wk = w1 + c * DW_K * DW_K;
+            // (the tap offsets and border predicates do not depend on (object, channel): hoisted out of this loop they are 49
+            // registers and 49 lane masks, which spill; behind this they are recomputed per item, a few hundred VALU instructions)
+            int y = yd, x = xd;
+            asm volatile("" : "+v"(y), "+v"(x));
+            // pass 1: all 49 loads, clamped addresses, no predicate near them; pass 2 selects and sums.  (As one loop hipcc sinks
+            // each load into the branch of its select and waits vmcnt(0) there: 49 serial round trips per item -- dw_tile's r2 note.)
+            float t[DW_K][DW_K];
+#pragma unroll
+            for (int ky = 0; ky < DW_K; ++ky) {
+                const int row = min(max(y + ky - DW_R, 0), h - 1) * w;
+#pragma unroll
+                for (int kx = 0; kx < DW_K; ++kx)  // (unsigned BYTE offsets on a uniform base, as in dw_tile: h*w < 2^29)
+                    t[ky][kx] = *(const float *)(src + 4u * (unsigned)(row + min(max(x + kx - DW_R, 0), w - 1)));
+            }
+#pragma unroll
+            for (int ky = 0; ky < DW_K; ++ky)
+                asm volatile("" : "+v"(t[ky][0]), "+v"(t[ky][1]), "+v"(t[ky][2]), "+v"(t[ky][3]), "+v"(t[ky][4]), "+v"(t[ky][5]), "+v"(t[ky][6]));
+            float acc = 0.0f;
+#pragma unroll
+            for (int ky = 0; ky < DW_K; ++ky) {
+                const int yy = y + ky - DW_R;
+                const bool yok = yy >= 0 && yy < h;
+#pragma unroll
+                for (int kx = 0; kx < DW_K; ++kx) {
+                    const int xx = x + kx - DW_R;
+                    acc = fmaf((yok && xx >= 0 && xx < w) ? t[ky][kx] : 0.0f, wk[ky * DW_K + kx], acc);
+                }
+            }
+            const float o = fmaf(acc + (b1 ? b1[c] : 0.0f), sc1 ? sc1[c] : 1.0f, sh1 ? sh1[c] : 0.0f);
+            dsh[ol][lane][c] = (_Float16)f16_sat(f16_relu(o));
+        }
+        for (int i = tid; i < ng * L16_P; i += L16_NT)
+            for (int c = Cp; c < 4; ++c) dsh[i >> 6][i & 63][c] = (_Float16)0.0f;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (LDS-only barriers: __syncthreads() would wait out the stores too)
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        for (int ol = 0; ol < ng; ++ol) {
+            f16x8 a[2];
+#pragma unroll
+            for (int pb = 0; pb < 2; ++pb) {
+                const f16x4 d = *(const f16x4 *)dsh[ol][pb * 32 + l31];
+                const f16x4 z = {(_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f, (_Float16)0.0f};
+                a[pb] = __builtin_shufflevector(lh ? z : d, z, 0, 1, 2, 3, 4, 5, 6, 7);  // k = 8 lh + 0..7: live in the low half only
+            }
+            _Float16 *dst = out + (long)(o0 + ol) * PW_CO * HW;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                const int co = co0 + cb * 32 + l31;
+#pragma unroll
+                for (int pb = 0; pb < 2; ++pb) {
+                    f32x16 acc;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[pb], wf[cb], acc, 0, 0, 0);
+                    // C/D layout: column = lane & 31 (output channel), registers 4 g .. 4 g + 3 = pixels 8 g + 4 (lane >> 5) + 0..3
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int p = p0 + pb * 32 + 8 * g + 4 * lh;
+                        if (p >= HW) continue;
+                        f32x4 v = {acc[4 * g] + bz[cb], acc[4 * g + 1] + bz[cb], acc[4 * g + 2] + bz[cb], acc[4 * g + 3] + bz[cb]};
+                        if (term) v += tv[cb][pb][g];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[j] = f16_sat(relu_out ? f16_relu(v[j]) : v[j]);
+                        *(f16x4 *)(dst + (long)co * HW + p) = __builtin_convertvector(v, f16x4);
+                    }
+                }
+            }
+        }
+        if (o0 + L16_OG < n) {  // (the next group's depthwise stage overwrites the table)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+    }
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The same fp32 contraction with the WEIGHTS RESIDENT IN REGISTERS (r4).  conv1x1_mfma_kernel streams a 16 KiB weight slice
@@ -1555,4 +1694,31 @@ extern "C" int manet_conv1x1_f16(const void *in, int64_t in_batch_stride, int B,
         hipLaunchKernelGGL(conv1x1_f16_kernel<false>, grid, dim3(H16_NT), 0, (hipStream_t)stream, (const _Float16 *)in, (long)in_batch_stride,
                            Cin, (long)HW, (const char *)wpk, b2, add, relu_out, out, head_w, head_b, head_out);
     return manet_check_launch("manet_conv1x1_f16");
+}
+
+// DynamicSegHead layer 1, per-object half, head_act="f16", one launch (head_layer1_object_f16_kernel): the bits of
+// manet_dwconv7x7_bn_relu_f16 (fp32 in) on planes [n][Cp][h][w] followed by manet_conv1x1_f16 with `add` = term
+extern "C" int manet_head_layer1_object_f16(const float *planes, int n, int Cp, int h, int w, const float *dw_weight,
+                                            const float *dw_bias, const float *bn_scale, const float *bn_shift, const void *wpk,
+                                            const float *b2, const float *term, int relu_out, void *out, manet_stream_t stream)
+{
+    if (!planes) return manet_set_error(MANET_E_INVALID, "planes is NULL");
+    if (!dw_weight) return manet_set_error(MANET_E_INVALID, "dw_weight is NULL");
+    if (!wpk) return manet_set_error(MANET_E_INVALID, "wpk is NULL");
+    if (!b2) return manet_set_error(MANET_E_INVALID, "b2 is NULL");
+    if (!out) return manet_set_error(MANET_E_INVALID, "out is NULL");
+    if (n < 1) return manet_set_error(MANET_E_INVALID, "n=%d must be at least 1", n);
+    if (Cp < 1 || Cp > 4) return manet_set_error(MANET_E_INVALID, "Cp=%d must be 1..4 (the per-object channels share one k block)", Cp);
+    if (h < 1 || w < 1) return manet_set_error(MANET_E_INVALID, "bad shape h=%d w=%d", h, w);
+    if (w % 2 != 0) return manet_set_error(MANET_E_INVALID, "w=%d must be even", w);
+    const int64_t HW = (int64_t)h * w;
+    if (HW % 8 != 0 || HW < 8 || HW > 0x7fffffff / 4)
+        return manet_set_error(MANET_E_INVALID, "h*w=%lld must be a multiple of 8, at least 8 (and at most 2^29 - 1)", (long long)HW);
+    if (((size_t)wpk & 15) != 0) return manet_set_error(MANET_E_INVALID, "wpk must be 16-byte aligned");
+    if (((size_t)term & 15) != 0) return manet_set_error(MANET_E_INVALID, "term must be 16-byte aligned");
+    if (((size_t)out & 15) != 0) return manet_set_error(MANET_E_INVALID, "out must be 16-byte aligned");
+    dim3 grid((unsigned)((HW + L16_P - 1) / L16_P));
+    hipLaunchKernelGGL(head_layer1_object_f16_kernel, grid, dim3(L16_NT), 0, (hipStream_t)stream, planes, n, Cp, h, w, dw_weight,
+                       dw_bias, bn_scale, bn_shift, (const uint4 *)wpk, b2, term, relu_out, (_Float16 *)out);
+    return manet_check_launch("manet_head_layer1_object_f16");
 }

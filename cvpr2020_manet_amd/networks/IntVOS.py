@@ -71,7 +71,9 @@ def _pointwise_mode(block=None):
 #   "f16" : every stage stores rn16(min(relu(.), 65504)) -- fp16, rounded once to nearest even, saturating, a NaN kept; the
 #           depthwise stages keep their fp32 fmaf chains (ops.dwconv7x7_bn_relu_f16), the 256-channel 1x1 stages multiply exact
 #           fp16 x fp16 products of the activation and the folded weight rounded once to fp16 on the fp16 MFMA with fp32
-#           accumulation (ops.conv1x1_f16); layer 1's shared-half term stays fp32 and is added unrounded; layer 4's ReLU and the
+#           accumulation (ops.conv1x1_f16); layer 1's shared-half term stays fp32 and is added unrounded, its per-object half
+#           (depthwise + 1x1 of up to 4 channels + the term) is one launch with those two kernels' bits
+#           (ops.head_layer1_object_f16); layer 4's ReLU and the
 #           output conv stay fused in fp32: logits are fp32 [n, 1, h, w].  Opt-in (IntVOS(cfg, fe, head_act="f16") /
 #           cfg.MODEL_HEAD_ACT / use_head_act); a head that is not eligible (DynamicSegHead._f16_ok) takes the "f32" route, same bits.
 _HEAD_ACT_MODES = ("f32", "f16")
@@ -534,14 +536,17 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
         k = self._folded(cs)
         scale, shift = k["scale1"], k["shift1"]
         w1, b1 = self.conv1.weight, self.conv1.bias
-        if act16:  # head_act="f16": the general three-launch form on the f16 kernels; the term is fp32, memoised as ever
+        if act16:  # head_act="f16": the term is fp32, memoised as ever; the per-object half is one launch where its shapes allow
             stamp = _memo_stamp(self, k)
             term = memo.get("term") if (memo is not None and memo.get("k") is k and memo.get("stamp") == stamp) else None
             if term is None:
                 term = self._shared_term_f16(shared, k, cs)
                 if memo is not None:
                     memo["k"], memo["term"], memo["stamp"] = k, term, stamp
-            p1 = ops.dwconv7x7_bn_relu_f16(per_object, w1[cs:], None if b1 is None else b1[cs:], scale=scale[cs:], shift=shift[cs:])
+            b1o = None if b1 is None else b1[cs:]
+            if ops.head_layer1_object_f16_ok(per_object):  # (up to 4 per-object channels: the same bits, one launch)
+                return ops.head_layer1_object_f16(per_object, w1[cs:], b1o, scale[cs:], shift[cs:], k["hw_object"], k["b2"], term=term)
+            p1 = ops.dwconv7x7_bn_relu_f16(per_object, w1[cs:], b1o, scale=scale[cs:], shift=shift[cs:])
             return ops.conv1x1_f16(p1, k["hw_object"], k["b2"], relu_out=True, add=term)
         p1 = ops.dwconv7x7_bn_relu(per_object, w1[cs:], b1[cs:], scale=scale[cs:], shift=shift[cs:])
         split = "sw_object" in k and ops.conv1x1_split_ok(p1, self.conv2.out_channels)
@@ -1541,7 +1546,8 @@ class IntVOS(nn.Module):
             if (native_maps and isinstance(dynamic_seghead, DynamicSegHead) and not dynamic_seghead.training
                     and not torch.is_grad_enabled()  # (eval() with grad mode on: the literal, differentiable head below -- ADVICE r5)
                     and dynamic_seghead.layer1.conv1.kernel_size == (7, 7) and (h * w) % 4 == 0
-                    # (head_act="f16": there is no fp16-output form of the fused layer-1 kernel -- the general route below)
+                    # (head_act="f16": head_inputs below, then forward_shared, whose per-object half is ONE launch of its own,
+                    # ops.head_layer1_object_f16 -- the fp16-output sibling of the kernel this branch runs)
                     and not dynamic_seghead._f16_ok(h, w, int(current_frame_embedding[n].shape[0]))):
                 # layer 1 straight from the two maps and the labels (r5): input assembly + per-object depthwise + its 1x1 + the
                 # (memoised) shared half + ReLU in one launch; layers 2-4 as ever

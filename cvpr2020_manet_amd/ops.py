@@ -1158,6 +1158,52 @@ def conv1x1_f16(x, weight, b2, relu_out=False, add=None, head_weight=None, head_
     return hout if head_weight is not None else out
 
 
+L1_F16_MAX_CP = 4  # per-object channels head_layer1_object_f16 takes (they share one k block of the MFMA)
+
+
+def head_layer1_object_f16_ok(per_object):
+    """shapes the fused per-object half of layer 1 takes: 1..4 per-object channels, w even, h*w a multiple of 8"""
+    if per_object.dim() != 4:
+        return False
+    n, cp, h, w = per_object.shape
+    return n >= 1 and 1 <= cp <= L1_F16_MAX_CP and w % 2 == 0 and (h * w) % 8 == 0 and h * w >= 8
+
+
+def head_layer1_object_f16(per_object, dw_weight, dw_bias, scale, shift, weight, b2, term=None, relu_out=True):
+    """DynamicSegHead layer 1, the per-object half under head_act="f16", in ONE launch (manet_head_layer1_object_f16): the bits
+    of conv1x1_f16(dwconv7x7_bn_relu_f16(per_object, dw_weight, dw_bias, scale=scale, shift=shift), weight, b2,
+    relu_out=relu_out, add=term) -- the same fp32 fmaf chains, one rounding to fp16, the same fp16 MFMA on a zero accumulator, the
+    same fp32 epilogue and store -- without the [n, Cp, h, w] fp16 planes in between and with the term read once, not once per
+    object.  per_object [n, Cp, h, w] fp32, Cp <= 4; dw_weight [Cp, 1, 7, 7]; dw_bias / scale / shift [Cp] or None; weight a
+    HalfWeight of Cp input channels; b2 [256]; term [1, 256, h, w] (or [256, h, w]) fp32 or None -> [n, 256, h, w] fp16."""
+    if not isinstance(weight, HalfWeight):
+        raise TypeError("weight must be an ops.HalfWeight")
+    _refuse_autograd("head_layer1_object_f16", per_object, dw_weight, dw_bias, scale, shift, b2, term)
+    _need_gpu(per_object, "per_object")
+    x = per_object.float().contiguous()
+    if not head_layer1_object_f16_ok(x):
+        raise ValueError("head_layer1_object_f16 needs [n, Cp <= %d, h, w] with w even and h*w a multiple of 8" % L1_F16_MAX_CP)
+    n, cp, h, w = x.shape
+    if tuple(dw_weight.shape) != (cp, 1, 7, 7):
+        raise ValueError("dw_weight must be [Cp, 1, 7, 7]")
+    if cp != weight.cin or b2.numel() != PW_COUT:
+        raise ValueError("per_object has %d channels, the packed weight %d; b2 must be [%d]" % (cp, weight.cin, PW_COUT))
+    wt = dw_weight.detach().float().contiguous()
+    bz, scale, shift = [None if t is None else t.detach().float().contiguous() for t in (dw_bias, scale, shift)]
+    if any(t is not None and t.numel() != cp for t in (bz, scale, shift)):
+        raise ValueError("dw_bias / scale / shift must be [Cp]")
+    b2 = b2.detach().float().contiguous()
+    if term is not None:
+        if term.numel() != PW_COUT * h * w:
+            raise ValueError("term must be [1, %d, h, w]" % PW_COUT)
+        term = term.detach().float().contiguous()
+    out = torch.empty((n, PW_COUT, h, w), dtype=torch.float16, device=x.device)
+    with _on(x.device):
+        _lib.call("manet_head_layer1_object_f16", x.data_ptr(), n, cp, h, w, wt.data_ptr(), _ptr(bz), _ptr(scale), _ptr(shift),
+                  weight.packed.data_ptr(), b2.data_ptr(), _ptr(term), int(bool(relu_out)), out.data_ptr(), _stream_ptr(x.device))
+    return out
+
+
 def relu_conv1x1_c1(x, weight, bias=None, relu_in=True):
     """DynamicSegHead's output layer in one pass over the activation (IntVOS.py:519,525): Conv2d(C, 1, 1) applied to
     max(x, 0) (relu_in) or to x.  x [B, C, h, w] fp32, weight [1, C, 1, 1], bias [1] or None -> [B, 1, h, w]."""

@@ -676,6 +676,24 @@ int manet_conv1x1_f16(const void *in, int64_t in_batch_stride, int B, int Cin, i
                       const float *add, int Cout, int relu_out, void *out, int out_f32, const float *head_w, const float *head_b,
                       float *head_out, manet_stream_t stream);
 
+/* head_act="f16", DynamicSegHead layer 1, the PER-OBJECT half in one launch: what manet_dwconv7x7_bn_relu_f16 (fp32 in) on
+ * `planes` followed by manet_conv1x1_f16 (Cin = Cp, add = term) computes, BIT FOR BIT, without the fp16 planes in between.
+ * For every object o < n, from its planes x[o][c] (c < Cp):
+ *   d_c  = rn16(min(relu(fmaf(taps_c + dw_bias[c], bn_scale[c], bn_shift[c])), 65504)), taps_c the depthwise kernels' fp32 fmaf
+ *          chain (ky outer, kx inner, zero padding);
+ *   acc  = sum_c fp16(w2[c][co]) * d_c: exact fp16 x fp16 products, fp32 accumulation, on the instruction manet_conv1x1_f16
+ *          uses (v_mfma_f32_32x32x16_f16: the live channels in k slots 0 .. Cp-1 of one block, zeros elsewhere, a zero accumulator);
+ *   out[o][co][p] = rn16(min(relu?((acc + b2[co]) + term[co][p]), 65504)), relu if relu_out != 0; a NaN stays a NaN.
+ * planes [n][Cp][h][w] fp32 contiguous; dw_weight [Cp][49]; dw_bias / bn_scale / bn_shift [Cp] or NULL (0 / 1 / 0); wpk the
+ * manet_conv1x1_f16_pack image for Cin = Cp (one 8 KiB chunk); b2 [256]; term [256][h*w] fp32 or NULL (nothing is added);
+ * out [n][256][h*w] fp16.  The term is read once per call, not once per object.
+ * MANET_E_INVALID before any launch, the text naming the argument: a NULL planes / dw_weight / wpk / b2 / out, n < 1, Cp outside
+ * 1..4, odd w, h*w not a multiple of 8 or below 8, wpk / term / out not 16-byte aligned.  Allocates nothing, never synchronises,
+ * enqueues on `stream`. */
+int manet_head_layer1_object_f16(const float *planes, int n, int Cp, int h, int w, const float *dw_weight, const float *dw_bias,
+                                 const float *bn_scale, const float *bn_shift, const void *wpk, const float *b2, const float *term,
+                                 int relu_out, void *out, manet_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Training path: what torch.autograd does for the reference's pure-PyTorch path
  * (train_stage1.py:126-156 back-propagates through IntVOS.forward) and what

@@ -3,9 +3,11 @@
 
   kernels     per stage at [3,256,120,214] and [2,256,120,214]: the fp32 depthwise against the f16 depthwise with both input types;
               conv1x1_mfma (manet_conv1x1_f32 and its add / fused-logits forms) and conv1x1_split against the f16 1x1 in its three
-              forms.  The entry points are called directly on preallocated, ROTATING buffers (a single hot activation sits in the
+              forms; layer 1's per-object half as the two launches it was (depthwise on [n,3] + 1x1 K=3 with the term) against
+              the fused kernel.  The entry points are called directly on preallocated, ROTATING buffers (a single hot activation sits in the
               memory-side cache): mean of N launches between two events, R repeats, the minimum and the maximum of the means.
-  head        the whole DynamicSegHead.forward_shared (layer 1's shared term memoised) as a captured graph, replayed: f32, split, f16.
+  head        the whole DynamicSegHead.forward_shared (layer 1's shared term memoised) as a captured graph, replayed: f32, split, f16, and f16
+              with layer 1's per-object half put back on its two launches.
   end to end  examples/propagate_clip.py's round at the roi bank, 480p, 2 objects: pointwise f32 / split / head_act f16, each under
               compute f32 and f16r; frames/s of every pass, and the f16 run's logit errors / mask flips against the fp32 head.
 The encoder and head weights are stand-ins: times do not depend on them, the error figures are THIS model's."""
@@ -22,6 +24,8 @@ from cvpr2020_manet_amd import _lib, ops  # noqa: E402
 from cvpr2020_manet_amd.networks import IntVOS as M  # noqa: E402
 
 NBUF = 6
+L1_TWO = "layer 1 object half: two launches (dw [n,3] f32->f16 + 1x1 K=3 add+relu f16)"
+L1_FUSED = "layer 1 object half: fused f16"
 
 
 def mean_us(fn, n):
@@ -53,6 +57,7 @@ def kernel_rows(n_ids, h, w, n, repeats):
     x16 = [t.half() for t in x32]
     p32 = [t[:, :3].contiguous() for t in x32]  # layer 1's per-object channels
     p16 = [t.half() for t in p32]
+    d16 = [torch.empty_like(t) for t in p16]  # the two-launch form's fp16 planes between its launches
     o32 = [torch.empty_like(t) for t in x32]
     o16 = [torch.empty_like(t) for t in x16]
     logit = torch.empty(n_ids, 1, h, w, device=dev)
@@ -79,6 +84,14 @@ def kernel_rows(n_ids, h, w, n, repeats):
         "1x1 K=256 -> logits: split": lambda i: lib.manet_conv1x1_x3_f32(P(x32[i % NBUF]), C * HW, n_ids, C, HW, P(sw.packed), b2, None, 256, 0, None, P(hw_), None, P(logit), st),
         "1x1 K=256 -> logits: f16": lambda i: lib.manet_conv1x1_f16(P(x16[i % NBUF]), C * HW, n_ids, C, HW, P(hw16.packed), b2, None, 256, 0, None, 0, P(hw_), None, P(logit), st),
     }
+
+    def two_launches(i):  # layer 1's per-object half as head_act="f16" ran it before the fused kernel
+        j = i % NBUF
+        return (lib.manet_dwconv7x7_bn_relu_f16(P(p32[j]), 0, n_ids, 3, h, w, P(wdw), bias, scale, shift, P(d16[j]), st)
+                or lib.manet_conv1x1_f16(P(d16[j]), 3 * HW, n_ids, 3, HW, P(hw163.packed), b2, P(term[j]), 256, 1, P(o16[j]), 0, None, None, None, st))
+
+    rows[L1_TWO] = two_launches
+    rows[L1_FUSED] = lambda i: lib.manet_head_layer1_object_f16(P(p32[i % NBUF]), n_ids, 3, h, w, P(wdw), bias, scale, shift, P(hw163.packed), b2, P(term[i % NBUF]), 1, P(o16[i % NBUF]), st)
     for k, fn in rows.items():
         assert fn(0) == 0, (k, lib.manet_last_error_string())
     return alternate(rows, n, repeats)
@@ -91,7 +104,10 @@ def head_rows(n_ids, h, w, n, repeats):
     emb = torch.relu(torch.randn(1, 100, h, w, device=dev)) * 0.3
     per = torch.rand(n_ids, 3, h, w, device=dev)
     rows, keep = {}, []
-    for name, pw, act in (("f32", "f32", "f32"), ("split", "split", "f32"), ("head_act f16", "f32", "f16")):
+    fused_ok = ops.head_layer1_object_f16_ok
+    for name, pw, act in (("f32", "f32", "f32"), ("split", "split", "f32"), ("head_act f16", "f32", "f16"),
+                          ("head_act f16, layer 1 object half as two launches", "f32", "f16")):
+        ops.head_layer1_object_f16_ok = (lambda per_object: False) if "two launches" in name else fused_ok
         head = M.DynamicSegHead(in_dim=103, embed_dim=256).to(dev).eval()
         head.load_state_dict(base.state_dict())
         for m in head.modules():
@@ -107,6 +123,7 @@ def head_rows(n_ids, h, w, n, repeats):
                 out = head.forward_shared(emb, per, memo=memo)
         keep.append((head, memo, out))
         rows[name] = lambda i, g=graph: g.replay()
+    ops.head_layer1_object_f16_ok = fused_ok
     return alternate(rows, n, repeats)
 
 
@@ -150,7 +167,10 @@ def main():
         torch.cuda.empty_cache()
         for sect in ("kernels_us", "head_us"):
             for k, v in res[sect][key].items():
-                print("%s %-42s %7.1f .. %7.1f us" % (key, k, v["min_us"], v["max_us"]), flush=True)
+                print("%s %-78s %7.1f .. %7.1f us" % (key, k, v["min_us"], v["max_us"]), flush=True)
+    # the module takes the fused form only if it wins outright at both shapes: its largest mean below the two launches' smallest
+    res["layer1_object_half_fused_accepted"] = all(v[L1_FUSED]["max_us"] < v[L1_TWO]["min_us"] for v in res["kernels_us"].values())
+    print("layer 1 object half, fused form accepted:", res["layer1_object_half_fused_accepted"], flush=True)
     if not a.skip_e2e:
         res["end_to_end"] = end_to_end(a.frames, a.rounds, a.passes)
         for k, v in res["end_to_end"].items():
