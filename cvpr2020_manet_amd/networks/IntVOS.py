@@ -53,6 +53,9 @@ cfg = _default_cfg
 #             fp32-class results (~2^-23 relative per product, fp32 accumulation; not the fmaf chain's bits) at 6/16 of the
 #             fp32 matrix pipe's time; opt-in;
 #   False / "framework" : the framework's GEMM as in r2.
+# The mode decides what a block's route table holds (_split_separable_conv2d._folded: k["pw"][slice], slice = "all" / "shared" /
+# "object" of the input channels): the fp32 [Cin, 256] tensor, an ops.SplitWeight, or None for the framework.  ONE method reads it,
+# _pw: the entry's kernel through ops.conv1x1 where ops.conv1x1_ok takes the shape, else F.conv2d with the same folded weights.
 # This global is only the default of heads built OUTSIDE an IntVOS; a model carries its own mode
 # (IntVOS(cfg, fe, pointwise=...) / cfg.MODEL_HEAD_POINTWISE), stamped on its _split_separable_conv2d blocks.
 MFMA_POINTWISE = "f32"
@@ -76,6 +79,8 @@ def _pointwise_mode(block=None):
 #           (ops.head_layer1_object_f16); layer 4's ReLU and the
 #           output conv stay fused in fp32: logits are fp32 [n, 1, h, w].  Opt-in (IntVOS(cfg, fe, head_act="f16") /
 #           cfg.MODEL_HEAD_ACT / use_head_act); a head that is not eligible (DynamicSegHead._f16_ok) takes the "f32" route, same bits.
+#           Its weights are the second route table, k["pw16"][slice]: an ops.HalfWeight, or None where a folded weight is not
+#           finite in fp16; _pw(..., act16=True) reads it.
 _HEAD_ACT_MODES = ("f32", "f16")
 
 
@@ -409,7 +414,8 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
         """Inference constants of the block, computed once and reused until a parameter or running statistic changes
         (r2 trace of examples/propagate_clip.py: re-folding both BatchNorms per call was 52 of the 76 kernel launches
         of a propagated frame).  Returns (scale1, shift1) of eval-mode bn1 and conv2 with eval-mode bn2 folded into
-        its weights -- bn2(conv2(x)) == conv2'(x) -- the latter also split at input channel `cs` (forward_shared)."""
+        its weights -- bn2(conv2(x)) == conv2'(x) -- the latter also split at input channel `cs` (forward_shared) -- and the
+        block's two route tables "pw" / "pw16" (the comment at MFMA_POINTWISE): slice -> kernel weight or None."""
         src = [self.bn1.weight, self.bn1.bias, self.bn1.running_mean, self.bn1.running_var, self.bn2.weight,
                self.bn2.bias, self.bn2.running_mean, self.bn2.running_var, self.conv2.weight, self.conv2.bias]
         act = getattr(self, "_head_act", "f32")
@@ -425,42 +431,42 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
             val = {"scale1": scale1.contiguous(), "shift1": shift1.contiguous(), "w2": w2, "b2": b2,
                    "b2_zero": torch.zeros_like(b2),  # (made here: exists before a driver forks its streams, prepare_bank)
                    "w2_shared": w2[:, :cs].contiguous(), "w2_object": w2[:, cs:].contiguous()}
-            mode = _pointwise_mode(self)
-            if self.conv2.out_channels == ops.PW_COUT and mode and w2.is_cuda:  # the weight transposed [Cin, Cout]
-                w2t = w2.reshape(w2.shape[0], w2.shape[1]).t().contiguous()
-                if mode in ("split", "split3"):  # ops.conv1x1_split: packed hi / (mid /) lo operand images
-                    np_ = 3 if mode == "split3" else 2
-                    val["sw"] = ops.SplitWeight(w2t, pieces=np_)
-                    if 0 < cs < w2t.shape[0]:
-                        val["sw_shared"], val["sw_object"] = ops.SplitWeight(w2t[:cs], pieces=np_), ops.SplitWeight(w2t[cs:], pieces=np_)
-                else:  # ops.conv1x1_mfma
-                    val["w2t"], val["w2t_shared"], val["w2t_object"] = w2t, w2t[:cs].contiguous(), w2t[cs:].contiguous()
-            val["mode"] = mode
-            if act == "f16" and self.conv2.out_channels == ops.PW_COUT and w2.is_cuda:
-                # head_act="f16": the folded weight (fp32, as above) rounded ONCE to fp16 and packed -- whole, and the shared /
-                # object slices of forward_shared.  A weight that is not finite in fp16 makes the block ineligible: no "hw"
-                # (one host read per fold; folds happen before a driver forks its streams or captures: prepare_bank)
-                if bool(torch.isfinite(w2.half()).all()):
-                    w2t = w2.reshape(w2.shape[0], w2.shape[1]).t().contiguous()
-                    val["hw"] = ops.HalfWeight(w2t)
-                    if 0 < cs < w2t.shape[0]:
-                        val["hw_shared"], val["hw_object"] = ops.HalfWeight(w2t[:cs]), ops.HalfWeight(w2t[cs:])
+            # the route tables: per slice of the input channels the kernel weight of the block's 1x1 stage -- "pw" on fp32
+            # activations (None: the framework's convolution with w2*), "pw16" under head_act="f16" (None: not eligible)
+            mode = val["mode"] = _pointwise_mode(self)
+            cuts = {"all": slice(None), "shared": slice(0, cs), "object": slice(cs, None)}
+            pw, pw16 = val["pw"], val["pw16"] = dict.fromkeys(cuts), dict.fromkeys(cuts)
+            if self.conv2.out_channels == ops.PW_COUT and w2.is_cuda:
+                w2t = w2.reshape(w2.shape[0], w2.shape[1]).t().contiguous()  # the weight transposed [Cin, Cout]
+                packed = cuts if 0 < cs < w2t.shape[0] else ("all",)  # (a packed image needs at least one input channel)
+                if mode in ("split", "split3"):  # ops.SplitWeight: packed hi / (mid /) lo operand images
+                    pw.update((s, ops.SplitWeight(w2t[cuts[s]], pieces=3 if mode == "split3" else 2)) for s in packed)
+                elif mode:  # "f32": the fp32 [Cin, 256] tensor itself
+                    pw.update((s, w2t[cut].contiguous()) for s, cut in cuts.items())
+                # head_act="f16": the folded weight (fp32, as above) rounded ONCE to fp16 and packed.  A weight that is not
+                # finite in fp16 makes the block ineligible: no entry (one host read per fold; folds happen before a driver
+                # forks its streams or captures: prepare_bank)
+                if act == "f16" and bool(torch.isfinite(w2.half()).all()):
+                    pw16.update((s, ops.HalfWeight(w2t[cuts[s]])) for s in packed)
         object.__setattr__(self, "_fold_cache", (key, val))  # plain attribute: not a buffer, not in the state dict
         return val
 
-    def _pointwise(self, y, k, which, bias, relu):
-        """bn2(conv2(y)) [+ relu2] on the depthwise stage's output: the fp32-MFMA 1x1 kernel when the shapes allow (256 output
-        channels, h*w a multiple of 4), else the framework's convolution with the same folded weights"""
-        skey = {"all": "sw", "shared": "sw_shared", "object": "sw_object"}[which]
-        if skey in k and ops.conv1x1_split_ok(y, self.conv2.out_channels):
-            b2 = k["b2"] if bias else k["b2_zero"]
-            return ops.conv1x1_split(y, k[skey], b2, relu_out=relu)
-        wkey = {"all": "w2t", "shared": "w2t_shared", "object": "w2t_object"}[which]
-        if wkey in k and ops.conv1x1_mfma_ok(y, self.conv2.out_channels):
-            b2 = k["b2"] if bias else k["b2_zero"]
-            return ops.conv1x1_mfma(y, k[wkey], b2, relu_out=relu)
-        w = {"all": "w2", "shared": "w2_shared", "object": "w2_object"}[which]
-        z = F.conv2d(y, k[w], k["b2"] if bias else None)
+    def _pw(self, y, k, which, bias, relu, add=None, head=None, act16=False, out_f32=False):
+        """bn2(conv2(y)) [+ add] [-> relu2] [-> the output layer head = (weight, bias) on the ReLU] on the depthwise stage's
+        output, for slice `which` of the folded weight: the kernel of the route table's entry where there is one and it takes the
+        shape (ops.conv1x1: 256 output channels, h*w a multiple of 4), else the framework's convolution with the same folded
+        weights, an output layer behind it on ops.relu_conv1x1_c1.  act16: the f16 table; its caller checked eligibility
+        (DynamicSegHead._f16_ok), and a missing kernel is an error there."""
+        weight = k["pw16" if act16 else "pw"][which]
+        if act16 or (weight is not None and ops.conv1x1_ok(y, weight, self.conv2.out_channels)):
+            hw, hb = (None, None) if head is None else head
+            return ops.conv1x1(y, weight, k["b2"] if bias else k["b2_zero"], relu_out=relu, add=add, head_weight=hw, head_bias=hb,
+                               out_f32=out_f32)
+        z = F.conv2d(y, k[{"all": "w2", "shared": "w2_shared", "object": "w2_object"}[which]], k["b2"] if bias else None)
+        if add is not None:
+            z += add  # (broadcast over the objects)
+        if head is not None:
+            return ops.relu_conv1x1_c1(z, head[0], head[1])
         return z.relu_() if relu else z
 
     def _f16_block_ok(self, cs=0):
@@ -472,24 +478,32 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
                 and c1.padding_mode == "zeros" and self.conv2.out_channels == ops.PW_COUT and self.conv2.kernel_size == (1, 1)
                 and c1.weight.is_cuda and c1.weight.dtype == torch.float32 and self.conv2.weight.dtype == torch.float32):
             return False
-        k = self._folded(cs)
-        return "hw" in k and (cs == 0 or "hw_object" in k)
+        pw16 = self._folded(cs)["pw16"]
+        return pw16["all"] is not None and (cs == 0 or pw16["object"] is not None)
 
     def _forward_f16(self, x, head=None):
         """the block on fp16 activations (head_act="f16"; the caller checked DynamicSegHead._f16_ok): x fp32 (layer 1) or fp16 ->
         fp16, or with head = (weight, bias) of the output layer the fp32 logits"""
         k = self._folded()
         y = ops.dwconv7x7_bn_relu_f16(x, self.conv1.weight, self.conv1.bias, scale=k["scale1"], shift=k["shift1"])
-        if head is not None:
-            return ops.conv1x1_f16(y, k["hw"], k["b2"], head_weight=head[0], head_bias=head[1])
-        return ops.conv1x1_f16(y, k["hw"], k["b2"], relu_out=True)
+        return self._pw(y, k, "all", True, head is None, head=head, act16=True)
 
-    def _shared_term_f16(self, shared, k, cs):
-        """layer 1's shared-half term in head_act="f16": the fp16 contraction of the shared channels' fp16 depthwise output,
-        left in fp32, unrounded; shared [b, cs, h, w] fp32 -> [b, 256, h, w] fp32"""
+    def _shared_term(self, shared, k, cs, memo, act16):
+        """Layer 1's shared-half term conv2'(dw(shared)), looked up in `memo` or computed and stored there: shared [b, cs, h, w]
+        fp32 -> [b, 256, h, w] fp32.  memo: a one-slot holder {"k", "term", "stamp"} or None; its term counts while `k` is the SAME
+        folded-constant object (mode and head_act are part of its key: a term never crosses modes) and the depthwise layer's
+        parameters are unchanged (_memo_stamp).  act16 (head_act="f16"): the fp16 contraction of the shared channels' fp16
+        depthwise output, left in fp32, unrounded."""
+        stamp = _memo_stamp(self, k)
+        if memo is not None and memo.get("k") is k and memo.get("stamp") == stamp and memo.get("term") is not None:
+            return memo["term"]
         w1, b1 = self.conv1.weight, self.conv1.bias
-        s1 = ops.dwconv7x7_bn_relu_f16(shared, w1[:cs], None if b1 is None else b1[:cs], scale=k["scale1"][:cs], shift=k["shift1"][:cs])
-        return ops.conv1x1_f16(s1, k["hw_shared"], k["b2_zero"], out_f32=True)
+        dw = ops.dwconv7x7_bn_relu_f16 if act16 else ops.dwconv7x7_bn_relu
+        s1 = dw(shared, w1[:cs], None if b1 is None else b1[:cs], scale=k["scale1"][:cs], shift=k["shift1"][:cs])
+        term = self._pw(s1, k, "shared", False, False, act16=act16, out_f32=act16)
+        if memo is not None:
+            memo["k"], memo["term"], memo["stamp"] = k, term, stamp
+        return term
 
     def forward(self, x, relu_in=False, defer_relu=False, head=None, act16=False):
         """relu_in / defer_relu (inference fast path only, used by DynamicSegHead): the block's last ReLU is left to the
@@ -503,13 +517,7 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
             k = self._folded()
             x = ops.dwconv7x7_bn_relu(x, self.conv1.weight, self.conv1.bias, scale=k["scale1"], shift=k["shift1"],
                                       relu_in=relu_in)
-            if head is not None:
-                if "sw" in k and ops.conv1x1_split_ok(x, self.conv2.out_channels):
-                    return ops.conv1x1_split(x, k["sw"], k["b2"], head_weight=head[0], head_bias=head[1])
-                if "w2t" in k and ops.conv1x1_mfma_ok(x, self.conv2.out_channels):
-                    return ops.conv1x1_mfma(x, k["w2t"], k["b2"], head_weight=head[0], head_bias=head[1])
-                return ops.relu_conv1x1_c1(self._pointwise(x, k, "all", True, False), head[0], head[1])
-            return self._pointwise(x, k, "all", True, not defer_relu)
+            return self._pw(x, k, "all", True, head is None and not defer_relu, head=head)
         assert not relu_in and not defer_relu
         if _train_all(self, x):  # training route "all" (use_train_kernels): the whole block on HIP, fwd + bwd
             x = ops.depthwise_conv2d(x, self.conv1.weight, self.conv1.bias) if _train_dw_ok(self, self.conv1, x) else self.conv1(x)
@@ -534,43 +542,22 @@ class _split_separable_conv2d(nn.Module):  # reference IntVOS.py:488-506
         object (a parameter change re-folds and drops it)."""
         cs = shared.shape[1]
         k = self._folded(cs)
-        scale, shift = k["scale1"], k["shift1"]
+        scale, shift = k["scale1"][cs:], k["shift1"][cs:]
         w1, b1 = self.conv1.weight, self.conv1.bias
         if act16:  # head_act="f16": the term is fp32, memoised as ever; the per-object half is one launch where its shapes allow
-            stamp = _memo_stamp(self, k)
-            term = memo.get("term") if (memo is not None and memo.get("k") is k and memo.get("stamp") == stamp) else None
-            if term is None:
-                term = self._shared_term_f16(shared, k, cs)
-                if memo is not None:
-                    memo["k"], memo["term"], memo["stamp"] = k, term, stamp
+            term = self._shared_term(shared, k, cs, memo, True)
             b1o = None if b1 is None else b1[cs:]
             if ops.head_layer1_object_f16_ok(per_object):  # (up to 4 per-object channels: the same bits, one launch)
-                return ops.head_layer1_object_f16(per_object, w1[cs:], b1o, scale[cs:], shift[cs:], k["hw_object"], k["b2"], term=term)
-            p1 = ops.dwconv7x7_bn_relu_f16(per_object, w1[cs:], b1o, scale=scale[cs:], shift=shift[cs:])
-            return ops.conv1x1_f16(p1, k["hw_object"], k["b2"], relu_out=True, add=term)
-        p1 = ops.dwconv7x7_bn_relu(per_object, w1[cs:], b1[cs:], scale=scale[cs:], shift=shift[cs:])
-        split = "sw_object" in k and ops.conv1x1_split_ok(p1, self.conv2.out_channels)
-        mfma = not split and "w2t_object" in k and ops.conv1x1_mfma_ok(p1, self.conv2.out_channels)
-        term = None
-        stamp = _memo_stamp(self, k)
-        if memo is not None and memo.get("k") is k and memo.get("stamp") == stamp and (split or mfma):
-            term = memo.get("term")
-        if term is None:
-            s1 = ops.dwconv7x7_bn_relu(shared, w1[:cs], b1[:cs], scale=scale[:cs], shift=shift[:cs])
-            if split:
-                term = ops.conv1x1_split(s1, k["sw_shared"], k["b2_zero"])
-            elif mfma:
-                term = ops.conv1x1_mfma(s1, k["w2t_shared"], k["b2_zero"])
-            if memo is not None and term is not None:
-                memo["k"], memo["term"], memo["stamp"] = k, term, stamp
-        if split:
-            # the shared half once, then the per-object half with it added in the epilogue (no broadcast-add pass)
-            return ops.conv1x1_split(p1, k["sw_object"], k["b2"], relu_out=not defer_relu, add=term)
-        if mfma:  # the same form on the fp32 matrix pipe
-            return ops.conv1x1_mfma(p1, k["w2t_object"], k["b2"], relu_out=not defer_relu, add=term)
-        y = self._pointwise(p1, k, "object", True, False)
-        y += self._pointwise(s1, k, "shared", False, False)  # broadcast over the objects
-        return y if defer_relu else y.relu_()
+                return ops.head_layer1_object_f16(per_object, w1[cs:], b1o, scale, shift, k["pw16"]["object"], k["b2"], term=term)
+            p1 = ops.dwconv7x7_bn_relu_f16(per_object, w1[cs:], b1o, scale=scale, shift=shift)
+            return self._pw(p1, k, "object", True, True, add=term, act16=True)
+        p1 = ops.dwconv7x7_bn_relu(per_object, w1[cs:], b1[cs:], scale=scale, shift=shift)
+        # the shared half once, then the per-object half with it added in its kernel's epilogue (no broadcast-add pass).  The
+        # term is memoised only where that kernel runs: on the framework's route it is computed every call and nothing is kept
+        wo = k["pw"]["object"]
+        kernel = wo is not None and ops.conv1x1_ok(p1, wo, self.conv2.out_channels)
+        term = self._shared_term(shared, k, cs, memo if kernel else None, False)
+        return self._pw(p1, k, "object", True, not defer_relu, add=term)
 
 
 def _memo_stamp(layer, k):
@@ -591,21 +578,16 @@ def _layer1_fused(layer, shared, global_map, local_map, labels, n_ids, size, mem
     caller then takes the general route)."""
     cs = shared.shape[1]
     k = layer._folded(cs)
-    if k.get("mode") != "f32" or "w2t_object" not in k or layer.conv1.in_channels != cs + 3 or layer.conv2.out_channels != ops.PW_COUT:
+    w2t_object = k["pw"]["object"]
+    if k["mode"] != "f32" or w2t_object is None or layer.conv1.in_channels != cs + 3 or layer.conv2.out_channels != ops.PW_COUT:
         return None
     # (eligibility from the shapes, BEFORE any launch: the depthwise stage keeps [1, cs, h, w] -- ADVICE r5)
     if shared.dim() != 4 or shared.dtype != torch.float32 or not ops.conv1x1_mfma_ok(shared, layer.conv2.out_channels):
         return None
     w1, b1 = layer.conv1.weight, layer.conv1.bias
-    stamp = _memo_stamp(layer, k)
-    term = memo.get("term") if (memo is not None and memo.get("k") is k and memo.get("stamp") == stamp) else None
-    if term is None:
-        s1 = ops.dwconv7x7_bn_relu(shared, w1[:cs], b1[:cs], scale=k["scale1"][:cs], shift=k["shift1"][:cs])
-        term = ops.conv1x1_mfma(s1, k["w2t_shared"], k["b2_zero"])
-        if memo is not None:
-            memo["k"], memo["term"], memo["stamp"] = k, term, stamp
+    term = layer._shared_term(shared, k, cs, memo, False)
     return ops.head_layer1_object(global_map, local_map, labels, n_ids, size, w1[cs:], None if b1 is None else b1[cs:],
-                                  k["scale1"][cs:], k["shift1"][cs:], k["w2t_object"], k["b2"], term, relu_out=True)
+                                  k["scale1"][cs:], k["shift1"][cs:], w2t_object, k["b2"], term, relu_out=True)
 
 
 class DynamicSegHead(nn.Module):  # reference IntVOS.py:509-525
@@ -708,6 +690,45 @@ def _run_head_parts(head, embedding_chw, maps, label_planes, n_ids, normalize_fi
             head, embedding_chw.new_empty((0, c + len(maps) + len(label_planes), h, w))):  # (a stand-in with x's channels)
         return ops.dynamic_seghead_train_parts(head, embedding_chw, maps, label_planes, n_ids, normalize_first)
     return head(ops.head_input_train(embedding_chw, maps, label_planes, n_ids, normalize_first))
+
+
+def _head_on_maps(head, emb_chw, global_map, local_map, labels, n_ids, size, inference, fused_inputs, norm_first, memo_of,
+                  ref_obj_ids):
+    """The propagation head on a frame (prop_seghead, IntVOS.py:663-673): its input [n_ids, C + 3, h, w] from the frame's
+    embedding `emb_chw`, the two match maps (h*w*n_ids values each) and the previous frame's label plane [h, w, 1], and the head
+    on it.  The first route that applies, in this order: the training route of the input (`fused_inputs`, train_inputs="fused");
+    layer 1 straight from the maps (_layer1_fused) + the tail; ops.head_inputs + _run_head; the reference's literal cat +
+    _run_head.  memo_of: () -> the frame's holder of layer 1's shared-half term (IntVOS._head_memo), or None."""
+    h, w = size
+    if fused_inputs and all(m.is_cuda and m.dtype == torch.float32 and m.numel() == h * w * n_ids for m in (global_map, local_map)):
+        # training route of the input (train_inputs="fused"): the maps and the label plane as they are
+        return _run_head_parts(head, emb_chw, [global_map, local_map], [labels], n_ids, normalize_first=norm_first)
+    if norm_first:  # (a local-map table of another type: the framework's ops below, on the normalised map)
+        global_map = (torch.sigmoid(global_map) - 0.5) * 2
+    plain_maps = (inference and global_map.is_cuda and global_map.dtype == torch.float32 and local_map.dtype == torch.float32
+                  and global_map.numel() == h * w * n_ids and local_map.numel() == h * w * n_ids)
+    if (plain_maps and isinstance(head, DynamicSegHead) and not head.training
+            and not torch.is_grad_enabled()  # (eval() with grad mode on: the literal, differentiable head below -- ADVICE r5)
+            and head.layer1.conv1.kernel_size == (7, 7) and (h * w) % 4 == 0
+            # (head_act="f16": head_inputs below, then forward_shared, whose per-object half is ONE launch of its own,
+            # ops.head_layer1_object_f16 -- the fp16-output sibling of the kernel this branch runs)
+            and not head._f16_ok(h, w, int(emb_chw.shape[0]))):
+        # layer 1 straight from the two maps and the labels (r5): input assembly + per-object depthwise + its 1x1 + the
+        # (memoised) shared half + ReLU in one launch; layers 2-4 as ever
+        emb_f = emb_chw if emb_chw.dtype == torch.float32 else emb_chw.float()
+        x1 = _layer1_fused(head.layer1, emb_f.unsqueeze(0), global_map, local_map, labels, n_ids, (h, w), memo=memo_of())
+        if x1 is not None:
+            return head._tail(x1)
+    if plain_maps:
+        # the three per-object channels written by one launch (no arange / compare / permute / cat kernels)
+        per_object = ops.head_inputs(global_map, local_map, labels, n_ids, (h, w))
+    else:
+        to_cat_previous_frame = (labels.float() == ref_obj_ids.float())
+        to_cat_nn_feature_n = global_map.squeeze(0).permute(2, 3, 0, 1)
+        to_cat_previous_frame = to_cat_previous_frame.unsqueeze(-1).permute(2, 3, 0, 1).float()
+        to_cat_prev_frame_nn_feature_n = local_map.squeeze(0).permute(2, 3, 0, 1)
+        per_object = torch.cat((to_cat_nn_feature_n, to_cat_prev_frame_nn_feature_n, to_cat_previous_frame), 1)
+    return _run_head(head, emb_chw, per_object, memo=memo_of() if inference else None)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -1021,11 +1042,10 @@ class IntVOS(nn.Module):
         k = layer._folded(cs)
         # head_act="f16" on an eligible head and grid: the term of THAT route (the f16 kernels' fp32 term)
         act16 = len(embeddings.shape) == 4 and head._f16_ok(int(embeddings.shape[2]), int(embeddings.shape[3]), cs)
-        if not act16 and (k.get("mode") != "f32" or "w2t_shared" not in k or layer.conv1.in_channels != cs + 3
+        if not act16 and (k["mode"] != "f32" or k["pw"]["shared"] is None or layer.conv1.in_channels != cs + 3
                           or layer.conv2.out_channels != ops.PW_COUT or layer.conv1.kernel_size != (7, 7)):
             return 0
         stamp = _memo_stamp(layer, k)
-        w1, b1 = layer.conv1.weight, layer.conv1.bias
         todo, done = [], 0
         for i in range(F_):
             e = embeddings[i]
@@ -1041,11 +1061,7 @@ class IntVOS(nn.Module):
         for i0 in range(0, len(todo), batch):
             part = todo[i0:i0 + batch]
             x = torch.stack([e if e.dtype == torch.float32 else e.float() for e, _ in part])
-            if act16:
-                terms = layer._shared_term_f16(x, k, cs)
-            else:
-                s1 = ops.dwconv7x7_bn_relu(x, w1[:cs], None if b1 is None else b1[:cs], scale=k["scale1"][:cs], shift=k["shift1"][:cs])
-                terms = ops.conv1x1_mfma(s1, k["w2t_shared"], k["b2_zero"])  # [b, 256, h, w]
+            terms = layer._shared_term(x, k, cs, None, act16)  # [b, 256, h, w]: one slice per frame's holder
             for j, (_, memo) in enumerate(part):
                 memo["k"], memo["term"], memo["stamp"] = k, terms[j:j + 1], stamp
             done += len(part)
@@ -1531,47 +1547,11 @@ class IntVOS(nn.Module):
                 prev_frame_nn_features_n = map_tab[frame_num[n]][interaction_num - (1 if newer_wins else 2)].unsqueeze(0)
                 local_map_dics = (local_map_tmp_dic, local_map_dist_dic)
 
-            # ---- head input [n_ids, C+3, h, w] (:663-673)
-            pred_ = None
-            if fused_inputs and all(m.is_cuda and m.dtype == torch.float32 and m.numel() == h * w * n_ids
-                                    for m in (nn_features_n, prev_frame_nn_features_n)):
-                # training route of the input (train_inputs="fused"): the maps and the label plane as they are
-                pred_ = _run_head_parts(dynamic_seghead, current_frame_embedding[n], [nn_features_n, prev_frame_nn_features_n],
-                                        [seq_previous_frame_label], n_ids, normalize_first=norm_first)
-            elif norm_first:  # (a local-map table of another type: the framework's ops below, on the normalised map)
-                nn_features_n = (torch.sigmoid(nn_features_n) - 0.5) * 2
-            native_maps = (inference and nn_features_n.is_cuda and nn_features_n.dtype == torch.float32
-                           and prev_frame_nn_features_n.dtype == torch.float32
-                           and nn_features_n.numel() == h * w * n_ids and prev_frame_nn_features_n.numel() == h * w * n_ids)
-            if (native_maps and isinstance(dynamic_seghead, DynamicSegHead) and not dynamic_seghead.training
-                    and not torch.is_grad_enabled()  # (eval() with grad mode on: the literal, differentiable head below -- ADVICE r5)
-                    and dynamic_seghead.layer1.conv1.kernel_size == (7, 7) and (h * w) % 4 == 0
-                    # (head_act="f16": head_inputs below, then forward_shared, whose per-object half is ONE launch of its own,
-                    # ops.head_layer1_object_f16 -- the fp16-output sibling of the kernel this branch runs)
-                    and not dynamic_seghead._f16_ok(h, w, int(current_frame_embedding[n].shape[0]))):
-                # layer 1 straight from the two maps and the labels (r5): input assembly + per-object depthwise + its 1x1 + the
-                # (memoised) shared half + ReLU in one launch; layers 2-4 as ever
-                emb_f = current_frame_embedding[n]
-                emb_f = emb_f if emb_f.dtype == torch.float32 else emb_f.float()
-                x1 = _layer1_fused(dynamic_seghead.layer1, emb_f.unsqueeze(0), nn_features_n, prev_frame_nn_features_n,
-                                   seq_previous_frame_label, n_ids, (h, w),
-                                   memo=self._head_memo(current_frame_embedding[n], dynamic_seghead))
-                if x1 is not None:
-                    pred_ = dynamic_seghead._tail(x1)
-            if pred_ is not None:
-                pass
-            elif native_maps:
-                # the three per-object channels written by one launch (no arange / compare / permute / cat kernels)
-                per_object = ops.head_inputs(nn_features_n, prev_frame_nn_features_n, seq_previous_frame_label, n_ids, (h, w))
-            else:
-                to_cat_previous_frame = (seq_previous_frame_label.float() == ref_obj_ids.float())
-                to_cat_nn_feature_n = nn_features_n.squeeze(0).permute(2, 3, 0, 1)
-                to_cat_previous_frame = to_cat_previous_frame.unsqueeze(-1).permute(2, 3, 0, 1).float()
-                to_cat_prev_frame_nn_feature_n = prev_frame_nn_features_n.squeeze(0).permute(2, 3, 0, 1)
-                per_object = torch.cat((to_cat_nn_feature_n, to_cat_prev_frame_nn_feature_n, to_cat_previous_frame), 1)
-            if pred_ is None:
-                pred_ = _run_head(dynamic_seghead, current_frame_embedding[n], per_object,
-                                  memo=self._head_memo(current_frame_embedding[n], dynamic_seghead) if inference else None)
+            # ---- head input [n_ids, C+3, h, w] (:663-673) and the head
+            emb_n = current_frame_embedding[n]
+            pred_ = _head_on_maps(dynamic_seghead, emb_n, nn_features_n, prev_frame_nn_features_n, seq_previous_frame_label, n_ids,
+                                  (h, w), inference, fused_inputs, norm_first, lambda: self._head_memo(emb_n, dynamic_seghead),
+                                  ref_obj_ids)
             dic_tmp[seq_names[n]] = pred_.permute(1, 0, 2, 3)
 
         if global_map_tmp_dic is None:

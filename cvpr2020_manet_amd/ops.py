@@ -964,41 +964,7 @@ def conv1x1_mfma(x, w2t, b2, relu_out=False, head_weight=None, head_bias=None, a
     head_weight [1, 256, 1, 1] (+ head_bias [1]): DynamicSegHead's output layer Conv2d(256, 1, 1)(relu(.)) (IntVOS.py:519,525)
     fused into the epilogue -- returns [B, 1, h, w], the 256-channel activation is never written.
     add [256, h, w] / [1, 256, h, w] fp32: added to every batch entry before relu_out (layer1's shared-embedding half)."""
-    _refuse_autograd("conv1x1_mfma", x, w2t, b2, head_weight, head_bias, add)
-    _need_gpu(x, "x")
-    x = x.float().contiguous()
-    B, cin, h, w = x.shape
-    if tuple(w2t.shape) != (cin, PW_COUT) or b2.numel() != PW_COUT:
-        raise ValueError("w2t must be [%d, %d] (ops.fold_pointwise), b2 [%d]" % (cin, PW_COUT, PW_COUT))
-    if not conv1x1_mfma_ok(x, PW_COUT):
-        raise ValueError("conv1x1_mfma needs h*w to be a multiple of 4")
-    w2t, b2 = w2t.detach().float().contiguous(), b2.detach().float().contiguous()
-    if add is not None:
-        if head_weight is not None:
-            raise ValueError("add and the fused output layer are exclusive")
-        if add.numel() != PW_COUT * h * w or add.dtype != torch.float32 or add.device != x.device:
-            raise ValueError("add must be [%d, h, w] fp32 on x's device" % PW_COUT)
-        add = add.contiguous()
-        out = torch.empty((B, PW_COUT, h, w), dtype=torch.float32, device=x.device)
-        with _on(x.device):
-            _lib.call("manet_conv1x1_add_f32", x.data_ptr(), cin * h * w, B, cin, h * w, w2t.data_ptr(), b2.data_ptr(),
-                      add.data_ptr(), PW_COUT, int(bool(relu_out)), out.data_ptr(), _stream_ptr(x.device))
-        return out
-    if head_weight is not None:
-        if head_weight.numel() != PW_COUT:
-            raise ValueError("head_weight must be [1, %d, 1, 1]" % PW_COUT)
-        hw = head_weight.detach().float().contiguous()
-        hb = None if head_bias is None else head_bias.detach().float().contiguous()
-        hout = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
-        with _on(x.device):
-            _lib.call("manet_conv1x1_head_f32", x.data_ptr(), cin * h * w, B, cin, h * w, w2t.data_ptr(), b2.data_ptr(), PW_COUT,
-                      0, None, hw.data_ptr(), _ptr(hb), hout.data_ptr(), _stream_ptr(x.device))
-        return hout
-    out = torch.empty((B, PW_COUT, h, w), dtype=torch.float32, device=x.device)
-    with _on(x.device):
-        _lib.call("manet_conv1x1_f32", x.data_ptr(), cin * h * w, B, cin, h * w, w2t.data_ptr(), b2.data_ptr(), PW_COUT,
-                  int(bool(relu_out)), out.data_ptr(), _stream_ptr(x.device))
-    return out
+    return _conv1x1("conv1x1_mfma", x, w2t, b2, relu_out, add, head_weight, head_bias)
 
 
 class SplitWeight:
@@ -1034,37 +1000,7 @@ def conv1x1_split(x, weight, b2, relu_out=False, add=None, head_weight=None, hea
     x [B, Cin, h, w] fp32; weight a SplitWeight; b2 [256] -> [B, 256, h, w].
     add [1, 256, h, w] (or [256, h, w]): added to every batch entry before relu_out -- layer1's shared-embedding half.
     head_weight / head_bias: DynamicSegHead's output layer fused (see conv1x1_mfma) -> [B, 1, h, w]."""
-    _refuse_autograd("conv1x1_split", x, b2, add, head_weight, head_bias)
-    _need_gpu(x, "x")
-    if not isinstance(weight, SplitWeight):
-        raise TypeError("weight must be an ops.SplitWeight")
-    x = x.float().contiguous()
-    B, cin, h, w = x.shape
-    if cin != weight.cin or b2.numel() != PW_COUT:
-        raise ValueError("x has %d channels, the packed weight %d; b2 must be [%d]" % (cin, weight.cin, PW_COUT))
-    if not conv1x1_split_ok(x, PW_COUT):
-        raise ValueError("conv1x1_split needs h*w to be a multiple of 4")
-    b2 = b2.detach().float().contiguous()
-    if add is not None:
-        if add.numel() != PW_COUT * h * w:
-            raise ValueError("add must be [1, %d, h, w]" % PW_COUT)
-        add = add.detach().float().contiguous()
-    hw = hb = hout = out = None
-    if head_weight is not None:
-        if head_weight.numel() != PW_COUT:
-            raise ValueError("head_weight must be [1, %d, 1, 1]" % PW_COUT)
-        if add is not None:
-            raise ValueError("add and the fused output layer are exclusive")
-        hw = head_weight.detach().float().contiguous()
-        hb = None if head_bias is None else head_bias.detach().float().contiguous()
-        hout = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
-    else:
-        out = torch.empty((B, PW_COUT, h, w), dtype=torch.float32, device=x.device)
-    with _on(x.device):  # (the weight's packing decides the symbol)
-        _lib.call("manet_conv1x1_x6_f32" if weight.pieces == 3 else "manet_conv1x1_x3_f32", x.data_ptr(), cin * h * w, B, cin,
-                  h * w, weight.packed.data_ptr(), b2.data_ptr(), _ptr(add), PW_COUT, int(bool(relu_out)), _ptr(out), _ptr(hw),
-                  _ptr(hb), _ptr(hout), _stream_ptr(x.device))
-    return hout if head_weight is not None else out
+    return _conv1x1("conv1x1_split", x, weight, b2, relu_out, add, head_weight, head_bias)
 
 
 F16_MAX = 65504.0  # the largest finite fp16: where the f16 head's stores saturate
@@ -1124,38 +1060,92 @@ def conv1x1_f16(x, weight, b2, relu_out=False, add=None, head_weight=None, head_
     add [1, 256, h, w] (or [256, h, w]) fp32: added unrounded to every batch entry before relu_out (layer 1's shared half).
     head_weight / head_bias: DynamicSegHead's output layer fused in fp32 (see conv1x1_mfma) -> [B, 1, h, w] fp32.
     out_f32: the result leaves as fp32, unrounded -- layer 1's shared-half term, which a later call takes as `add`."""
-    _refuse_autograd("conv1x1_f16", x, b2, add, head_weight, head_bias)
+    return _conv1x1("conv1x1_f16", x, weight, b2, relu_out, add, head_weight, head_bias, out_f32)
+
+
+def _conv1x1(name, x, weight, b2, relu_out, add, head_weight, head_bias, out_f32=False):
+    """The one body of conv1x1_mfma / conv1x1_split / conv1x1_f16 (`name` says which): refuses autograd, checks and normalises
+    the operands, allocates the output and makes the call.  What differs between the three is spelled out where it differs: the
+    input's type (f16 takes fp16 as it is, the others convert to fp32), the weight (a checked fp32 [Cin, 256] tensor or a packed
+    image), `add` (mfma refuses one that is not fp32 on x's device, the others convert) and the symbol with its argument order."""
+    mfma, f16 = name == "conv1x1_mfma", name == "conv1x1_f16"
+    _refuse_autograd(name, x, weight, b2, add, head_weight, head_bias)
     _need_gpu(x, "x")
-    if not isinstance(weight, HalfWeight):
-        raise TypeError("weight must be an ops.HalfWeight")
-    if x.dtype != torch.float16:
+    if not mfma and not isinstance(weight, HalfWeight if f16 else SplitWeight):
+        raise TypeError("weight must be an ops.%s" % ("HalfWeight" if f16 else "SplitWeight"))
+    if f16 and x.dtype != torch.float16:
         raise ValueError("x must be fp16 (the f16 depthwise kernel's output)")
-    x = x.contiguous()
+    x = x.contiguous() if f16 else x.float().contiguous()
     B, cin, h, w = x.shape
-    if cin != weight.cin or b2.numel() != PW_COUT:
-        raise ValueError("x has %d channels, the packed weight %d; b2 must be [%d]" % (cin, weight.cin, PW_COUT))
-    if not conv1x1_f16_ok(x, PW_COUT):
-        raise ValueError("conv1x1_f16 needs h*w to be a multiple of 8")
+    if mfma:
+        if tuple(weight.shape) != (cin, PW_COUT) or b2.numel() != PW_COUT:
+            raise ValueError("w2t must be [%d, %d] (ops.fold_pointwise), b2 [%d]" % (cin, PW_COUT, PW_COUT))
+        wt = weight.detach().float().contiguous()
+    else:
+        if cin != weight.cin or b2.numel() != PW_COUT:
+            raise ValueError("x has %d channels, the packed weight %d; b2 must be [%d]" % (cin, weight.cin, PW_COUT))
+        wt = weight.packed
+    if not _CONV1X1_OK[name](x, PW_COUT):
+        raise ValueError("%s needs h*w to be a multiple of %d" % (name, 8 if f16 else 4))
     b2 = b2.detach().float().contiguous()
     if add is not None:
-        if add.numel() != PW_COUT * h * w:
-            raise ValueError("add must be [1, %d, h, w]" % PW_COUT)
-        add = add.detach().float().contiguous()
+        if head_weight is not None:
+            raise ValueError("add and the fused output layer are exclusive")
+        if add.numel() != PW_COUT * h * w or (mfma and (add.dtype != torch.float32 or add.device != x.device)):
+            raise ValueError("add must be [%d, h, w] fp32 on x's device" % PW_COUT if mfma else "add must be [1, %d, h, w]" % PW_COUT)
+        add = add.contiguous() if mfma else add.detach().float().contiguous()
     hw = hb = hout = out = None
     if head_weight is not None:
         if head_weight.numel() != PW_COUT:
             raise ValueError("head_weight must be [1, %d, 1, 1]" % PW_COUT)
-        if add is not None:
-            raise ValueError("add and the fused output layer are exclusive")
         hw = head_weight.detach().float().contiguous()
         hb = None if head_bias is None else head_bias.detach().float().contiguous()
         hout = torch.empty((B, 1, h, w), dtype=torch.float32, device=x.device)
     else:
-        out = torch.empty((B, PW_COUT, h, w), dtype=torch.float32 if out_f32 else torch.float16, device=x.device)
+        out = torch.empty((B, PW_COUT, h, w), dtype=torch.float16 if f16 and not out_f32 else torch.float32, device=x.device)
+    relu = int(bool(relu_out))
     with _on(x.device):
-        _lib.call("manet_conv1x1_f16", x.data_ptr(), cin * h * w, B, cin, h * w, weight.packed.data_ptr(), b2.data_ptr(), _ptr(add),
-                  PW_COUT, int(bool(relu_out)), _ptr(out), int(bool(out_f32)), _ptr(hw), _ptr(hb), _ptr(hout), _stream_ptr(x.device))
-    return hout if head_weight is not None else out
+        head = (x.data_ptr(), cin * h * w, B, cin, h * w, wt.data_ptr(), b2.data_ptr())  # (how every one of the symbols begins)
+        stream = _stream_ptr(x.device)
+        if f16:
+            _lib.call("manet_conv1x1_f16", *head, _ptr(add), PW_COUT, relu, _ptr(out), int(bool(out_f32)), _ptr(hw), _ptr(hb),
+                      _ptr(hout), stream)
+        elif not mfma:  # (the weight's packing decides the symbol)
+            _lib.call("manet_conv1x1_x6_f32" if weight.pieces == 3 else "manet_conv1x1_x3_f32", *head, _ptr(add), PW_COUT, relu,
+                      _ptr(out), _ptr(hw), _ptr(hb), _ptr(hout), stream)
+        elif add is not None:
+            _lib.call("manet_conv1x1_add_f32", *head, add.data_ptr(), PW_COUT, relu, out.data_ptr(), stream)
+        elif hw is not None:
+            _lib.call("manet_conv1x1_head_f32", *head, PW_COUT, 0, None, hw.data_ptr(), _ptr(hb), hout.data_ptr(), stream)
+        else:
+            _lib.call("manet_conv1x1_f32", *head, PW_COUT, relu, out.data_ptr(), stream)
+    return out if hout is None else hout
+
+
+_CONV1X1_OK = {"conv1x1_mfma": conv1x1_mfma_ok, "conv1x1_split": conv1x1_split_ok, "conv1x1_f16": conv1x1_f16_ok}
+
+
+def _conv1x1_of(weight):
+    """the typed wrapper's name for a kernel weight: an fp32 [Cin, 256] tensor, a SplitWeight or a HalfWeight"""
+    if isinstance(weight, torch.Tensor) and weight.dtype == torch.float32:
+        return "conv1x1_mfma"
+    if isinstance(weight, (SplitWeight, HalfWeight)):
+        return "conv1x1_f16" if isinstance(weight, HalfWeight) else "conv1x1_split"
+    raise TypeError("weight must be an fp32 [Cin, %d] tensor, an ops.SplitWeight or an ops.HalfWeight" % PW_COUT)
+
+
+def conv1x1_ok(x, weight, cout=PW_COUT):
+    """the kernel of `weight`'s type takes x's shape (conv1x1_mfma_ok / conv1x1_split_ok / conv1x1_f16_ok)"""
+    return _CONV1X1_OK[_conv1x1_of(weight)](x, cout)
+
+
+def conv1x1(x, weight, b2, relu_out=False, add=None, head_weight=None, head_bias=None, out_f32=False):
+    """The 256-channel 1x1 stage on the kernel of `weight`'s type: an fp32 [Cin, 256] tensor -> conv1x1_mfma, a SplitWeight ->
+    conv1x1_split, a HalfWeight -> conv1x1_f16 (x fp16; the only one that takes out_f32).  Anything else is a TypeError."""
+    name = _conv1x1_of(weight)
+    if out_f32 and name != "conv1x1_f16":
+        raise ValueError("out_f32 is the f16 kernel's (an ops.HalfWeight)")
+    return _conv1x1(name, x, weight, b2, relu_out, add, head_weight, head_bias, out_f32)
 
 
 L1_F16_MAX_CP = 4  # per-object channels head_layer1_object_f16 takes (they share one k block of the MFMA)

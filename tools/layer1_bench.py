@@ -38,7 +38,7 @@ for n_ids, h, w in ((3, 120, 214), (2, 120, 214), (6, 180, 320)):
         # the kernel -- and a single hot term sits in the memory-side cache; for exact kernel times run this script under
         # `rocprofv3 --kernel-trace --stats`)
         terms = [memo["term"].clone() for _ in range(10)]
-        args = (w1[100:], b1[100:], k["scale1"][100:], k["shift1"][100:], k["w2t_object"], k["b2"])
+        args = (w1[100:], b1[100:], k["scale1"][100:], k["shift1"][100:], k["pw"]["object"], k["b2"])
         turn = [0]
 
         def fused():
@@ -48,7 +48,7 @@ for n_ids, h, w in ((3, 120, 214), (2, 120, 214), (6, 180, 320)):
         def three():
             po = ops.head_inputs(gmap, lmap, lab, n_ids, (h, w))
             p1 = ops.dwconv7x7_bn_relu(po, w1[100:], b1[100:], scale=k["scale1"][100:], shift=k["shift1"][100:])
-            return ops.conv1x1_mfma(p1, k["w2t_object"], k["b2"], relu_out=True, add=memo["term"])
+            return ops.conv1x1_mfma(p1, k["pw"]["object"], k["b2"], relu_out=True, add=memo["term"])
 
         assert torch.equal(fused(), three()) and torch.equal(M._layer1_fused(l1, emb, gmap, lmap, lab, n_ids, (h, w), memo=memo), three())
         best = {"fused": 1e9, "three launches": 1e9}
